@@ -491,6 +491,36 @@ def committed_traffic(n_frames: int, ln_fold: bool):
                   f"src {me['src_sha256'][:12]}); {len(seen)} older file(s) ignored - run tools/prof_round.sh on this build"), None
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path: str, tensors: dict, limit: int = DUMP_LIMIT_BYTES) -> dict:
+    """Write each tensor as path/<name>.npy (floating point as float32, integers as float64: exact below 2**53), at most `limit`
+    bytes in all.  An array over its share of the budget keeps a fixed, seeded sample of its rows (last axis intact), and
+    <name>_rows.npy lists the kept row numbers.  Returns {file name: shape written}."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrs = {}
+    for name, t in tensors.items():
+        t = t.detach().cpu()
+        arrs[name] = (t.float() if t.is_floating_point() else t.double()).numpy()
+    written, left = {}, limit - 4096 * len(arrs)      # (headroom for the .npy headers)
+    for i, name in enumerate(sorted(arrs, key=lambda n: arrs[n].nbytes)):       # the small ones first, whole
+        a = arrs[name]
+        share = left // (len(arrs) - i)
+        if a.nbytes > share:
+            rows = a.reshape(-1, a.shape[-1] if a.ndim > 1 else 1)
+            keep = np.sort(np.random.default_rng(0).choice(len(rows), size=max(1, share // (rows[0].nbytes + 8)), replace=False))
+            a = rows[keep]
+            np.save(os.path.join(path, f"{name}_rows.npy"), keep.astype(np.float64))
+            written[f"{name}_rows.npy"] = list(keep.shape)
+            left -= keep.size * 8
+        np.save(os.path.join(path, f"{name}.npy"), a)
+        written[f"{name}.npy"] = list(a.shape)
+        left -= a.nbytes
+    return written
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -516,7 +546,12 @@ def main():
                          "value = frames of that one video / s (STRONG scaling)")
     ap.add_argument("--no-long-form", action="store_true", help="N > 1: skip the extra (non-headline) sharded 4096-frame video measurement")
     ap.add_argument("--no-comm-probe", action="store_true", help="skip the RCCL probe (init + timed all-reduce of the gradient bucket)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what rank 0's last timed step returned (top-k indices, scores, features) as "
+                         "DIR/<name>.npy, float32 / float64, at most 64 MB in all; the inputs are seeded, so two builds compare output for output")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if not torch.cuda.is_available():
         sys.exit("bench.py needs an MI355X (no CPU path in the product); use gpurun")
@@ -623,9 +658,9 @@ def main():
         if shard:      # frames of the one video over the ranks -> all-gather [T/N, 768] shards -> replicated selector + top-k
             feats = scorer.encode(pixels, shard_frames=True)
             sc, _ = scorer.score(feats, txt)
-            out["idx"], out["scores"] = ops.topk_sorted(sc, k), sc
+            out["idx"], out["scores"], out["feats"] = ops.topk_sorted(sc, k), sc, feats
         else:
-            out["idx"], out["scores"], _ = scorer(pixels, txt, k)
+            out["idx"], out["scores"], out["feats"] = scorer(pixels, txt, k)
 
     step_ms, rank_sec = [], []
     sampler = GpuSampler(dev)
@@ -637,6 +672,10 @@ def main():
     frames = B * T * (1 if shard else world) * a.steps      # sharded: the ranks share ONE video (strong scaling)
     fps = frames / sec
     assert out["idx"].shape == (B, min(T, k)) and bool((out["idx"][:, 1:] > out["idx"][:, :-1]).all())
+    dumped = None
+    if a.dump_outputs and rank == 0:      # the last timed step's results, before the variants below reuse `out`
+        dumped = {"dir": a.dump_outputs, "rank": 0,
+                  "arrays": dump_outputs(a.dump_outputs, {"topk_idx": out["idx"], "scores": out["scores"], "features": out["feats"]})}
 
     # ---- opt-in variant (NOT the headline): last transformer block evaluated for the class-token row only --------
     # (its other 256 token rows have no consumer; identical features, 3.5 % fewer executed FLOPs; reported separately
@@ -831,7 +870,7 @@ def main():
                          "score_select_bf16_operands": round(sel16_sec * 1e3, 3), "bf16_keeps_fraction_of_fp32_topk": round(keep16, 4),
                          "note": "score_select = clip cosine + scoring head + top-k on resident features, exact fp32 (used for `value`); "
                                  "_bf16_operands = the same with FrameScorer(selector_precision='bf16'), the reference's inference precision"},
-            "roofline": roof, "cpu_baseline": cpu, "comm": comm,
+            "roofline": roof, "cpu_baseline": cpu, "comm": comm, "dumped_outputs": dumped,
             "launcher": "torch.distributed.run" if (world > 1 and not os.environ.get("TSPO_SELF_SPAWNED")) else
                         ("self-spawn" if world > 1 else "single process"),
         }

@@ -389,3 +389,26 @@ def test_bench_line_explains_itself_and_times_the_dp_path():
     comm = line["comm"]
     assert comm["world"] == 1 and comm["backend"] == "nccl" and comm["sum_correct"] and comm["distinct_devices"] == 1
     assert comm["ranks"][0]["pci"] == roof["gpu_state"]["pci"]
+
+
+def test_bench_dump_outputs_of_the_last_timed_step(tmp_path):
+    """`--dump-outputs DIR`: what the timed path returned in its last step, as .npy files (float32 / float64), with seeded inputs:
+    two runs with the same arguments dump the same indices, and the indices are the sorted top-k of the dumped scores."""
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--frames", "64", "--topk", "8", "--steps", "3", "--warmup", "1",
+            "--no-cpu-baseline", "--no-pruned", "--no-720p", "--no-rollouts", "--no-comm-probe", "--no-profile"]
+    got = []
+    for run in ("a", "b"):
+        r = subprocess.run(base + ["--dump-outputs", str(tmp_path / run)], env=_clean_env(), cwd=ROOT, capture_output=True,
+                           text=True, timeout=900)
+        _ok(r, f"bench_dump_outputs_{run}")
+        line = [l for l in _json_lines(r.stdout) if "metric" in l][0]
+        assert line["steps"] == 3 and line["ms_per_step"] > 0
+        assert line["dumped_outputs"]["arrays"] == {"topk_idx.npy": [1, 8], "scores.npy": [1, 64], "features.npy": [1, 64, 768]}
+        arr = {n: np.load(tmp_path / run / f"{n}.npy") for n in ("topk_idx", "scores", "features")}
+        assert arr["topk_idx"].dtype == np.float64 and arr["scores"].dtype == arr["features"].dtype == np.float32
+        assert np.isfinite(arr["scores"]).all() and np.isfinite(arr["features"]).all()
+        assert arr["topk_idx"][0].tolist() == sorted(np.argsort(-arr["scores"][0], kind="stable")[:8].tolist())
+        got.append(arr)
+    assert np.array_equal(got[0]["topk_idx"], got[1]["topk_idx"])
+    np.testing.assert_allclose(got[0]["scores"], got[1]["scores"], rtol=0, atol=1e-5)
+    np.testing.assert_allclose(got[0]["features"], got[1]["features"], rtol=0, atol=1e-5)

@@ -181,7 +181,8 @@ def test_hf_entry_points_and_merge_flow(tmp_path):
     assert isinstance(back, TSPOModel) and back.dtype == torch.bfloat16 and isinstance(back.selector, MultiModal_Align)
     sd1, sd2 = model.state_dict(), back.state_dict()
     assert sorted(sd1) == sorted(sd2) and len([k for k in sd2 if k.startswith("selector.")]) == 12
-    assert all(torch.equal(sd1[k].to(torch.bfloat16), sd2[k]) for k in sd1)
+    # device_map="auto" places the model on the GPU where there is one: compare on the host
+    assert all(torch.equal(sd1[k].to(torch.bfloat16), sd2[k].cpu()) for k in sd1)
 
     # a DeepSpeed-style training checkpoint: four shards, the selector ("multiModal_align.*") in the last one
     shards = tmp_path / "train_ckpt"
@@ -202,9 +203,9 @@ def test_hf_entry_points_and_merge_flow(tmp_path):
     again = TSPOModel.from_pretrained(str(d2), attn_implementation="flash_attention_2", torch_dtype=torch.bfloat16,
                                       device_map="auto")
     for k, v in sel.items():
-        assert torch.equal(again.selector.state_dict()[k], v.to(torch.bfloat16))
+        assert torch.equal(again.selector.state_dict()[k].cpu(), v.to(torch.bfloat16))
     for k, v in clip_model.state_dict().items():
-        assert torch.equal(again.state_dict()[k], v)
+        assert torch.equal(again.state_dict()[k].cpu(), v)
     assert sorted(tio.extract_selector_state(again.state_dict())) == sorted(sel)      # "selector." prefix of the merged model
 
 

@@ -131,18 +131,26 @@ def test_train_step(golden, case):
             assert abs(gr.double().abs().sum().item() - sums[1]) <= 1e-4 * max(sums[1], 1e-12)
     # ffn_o never receives a gradient
     assert grads["temporal.ffn_o.weight"].abs().sum() == 0
-    # AdamW step incl. clip-norm
+    # AdamW step incl. clip-norm: every element on the reference's own gradients and norm, and on the gradients computed above
+    # wherever the reference's gradient is above the 1e-6 floor of the gradient checks.  Below it a gradient is zero up to rounding
+    # (temporal.Self_k.bias: a key bias shifts a whole softmax row; dead ReLU units of mlp.*), and the step-1 update
+    # lr * g / (|g| + eps) follows that rounding noise, which differs from one CPU to another.
     flat = torch.cat([grads[n].flatten() for n in O.SELECTOR_KEYS if "ffn_o" not in n])
     tn = flat.norm().item()
     assert abs(tn - float(g[f"{name}.gradnorm"])) < 1e-4 * max(1.0, tn)
-    scale = O.clip_grad_scale(tn, 1.0)
+    scale, scale_ref = O.clip_grad_scale(tn, 1.0), O.clip_grad_scale(float(g[f"{name}.gradnorm"]), 1.0)
     for pn in O.SELECTOR_KEYS:
         if "ffn_o" in pn:
             continue
-        p0 = T_(state[pn])
-        p1, _, _ = O.adamw_step(p0, grads[pn], torch.zeros_like(p0), torch.zeros_like(p0), 1, 5e-4,
+        p0 = T_(state[pn]).flatten()[:256]
+        after = g[f"{name}.after.{pn}"]
+        stored = (g[f"{name}.grad.{pn}"] if f"{name}.grad.{pn}" in g.files else g[f"{name}.gradsl.{pn}"]).flatten()[:256]
+        p1, _, _ = O.adamw_step(p0, T_(stored), torch.zeros_like(p0), torch.zeros_like(p0), 1, 5e-4, grad_scale=scale_ref)
+        np.testing.assert_allclose(p1.numpy(), after, rtol=1e-5, atol=1e-6)
+        p1, _, _ = O.adamw_step(p0, grads[pn].flatten()[:256], torch.zeros_like(p0), torch.zeros_like(p0), 1, 5e-4,
                                 grad_scale=scale)
-        np.testing.assert_allclose(p1.flatten()[:256].numpy(), g[f"{name}.after.{pn}"], rtol=1e-5, atol=1e-6)
+        real = np.abs(stored) > 1e-6
+        np.testing.assert_allclose(p1.numpy()[real], after[real], rtol=1e-5, atol=1e-6)
 
 
 @pytest.mark.parametrize("name", ["c2", "c4"])
