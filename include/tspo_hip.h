@@ -187,6 +187,27 @@ int tspo_selector_backward(const tspo_selector_weights* w, const float* img, con
  * ReLU, residual, cosine) stays fp32 - fewer roundings than the reference's bf16 module, whose every intermediate is bf16.
  * Not for the greedy-index parity claims (those use flags = 0) and not accepted by the backward calls. */
 #define TSPO_SEL_BF16 4
+/* TSPO_SEL_BF16_MIXED: the reference's bf16 TRAINING precision (`--bf16 --torch_dtype bfloat16`, train_deepspeed.sh:33-34;
+ * DeepSpeed bf16 with fp32 master weights) for forward AND backward.  Accepted by tspo_selector_forward_ex,
+ * tspo_selector_backward_ex, tspo_policy_backward and tspo_policy_backward_ex; combines with TSPO_SEL_ACCUMULATE; exclusive with
+ * TSPO_SEL_BF16X3 and with TSPO_SEL_BF16 (TSPO_EINVAL).  With r(x) = round-to-nearest-even to bf16 in registers and fp32
+ * accumulation everywhere:
+ *   forward   qkv = r(x_pe) r(Wqkv)^T + bqkv,  h1 = relu(r(ctx) r(W1)^T + b1),  h2 = r(h1) r(W2)^T + b2 + x
+ *             (exactly the arithmetic of TSPO_SEL_BF16: bitwise the same scores);
+ *   backward  dW2 = r(dh2)^T r(h1),  dh1 = (r(dh2) r(W2)) * [h1 > 0],  dW1 = r(dh1)^T r(ctx),  dctx = r(dh1) r(W1),
+ *             dWqkv = r(dqkv)^T r(x_pe).
+ * The positional add, banded softmax and its backward, the cosine score and its backward, and the bias gradients (column sums of
+ * the UNROUNDED fp32 dh2 / dh1 / dqkv) stay fp32, as do the activations the forward saves (no bf16 copies are kept: the backward
+ * rounds the saved fp32 values in registers), the gradient buffers and the optimiser.  A backward with this flag needs a
+ * workspace written by a forward with this flag, and a forward with it is meant for a backward with it (flags = 0 pairs with
+ * flags = 0): the library keeps no state and does not check the pairing.  Weight-gradient GEMMs are single-pass
+ * v_mfma_f32_16x16x32_bf16 kernels in every form the exact path selects (fused or not, whole-contraction 64x64 tiles or
+ * split contraction).  Deterministic like every other mode. */
+#define TSPO_SEL_BF16_MIXED 8
+/* The option bits an entry point accepts: entry 0 tspo_selector_forward_ex, 1 tspo_selector_backward_ex, 2 tspo_policy_backward /
+ * tspo_policy_backward_ex.  Lets a caller test whether the loaded library takes a flag without calling it.  Touches no device.
+ * Unknown entry: TSPO_EINVAL (negative).                                                                                          */
+int tspo_selector_supported_flags(int entry);
 int tspo_selector_forward_ex(const tspo_selector_weights* w, const float* img, const float* txt, const float* clip,
                              int B, int T, int D, int H, int M, int window, float tau,
                              float* scores, float* temporal_attn,

@@ -1206,6 +1206,60 @@ __global__ __launch_bounds__(256) void gemm_f32_tn_kernel(const float* __restric
     }
 }
 
+// bf16-operand form of the kernel above (TSPO_SEL_BF16_MIXED; the fallback for NI or NJ not a multiple of 128): same 64x64 wave tile
+// and interleaved feature map, 32 contraction rows per k-step - lane (l15, q) reads rows 8q..8q+7 (8 float4 per operand, 4 feature
+// tiles each), rounds them to bf16 in registers and issues one v_mfma_f32_16x16x32_bf16 per tile pair.
+__global__ __launch_bounds__(256) void gemm_f32_tn_bf16_kernel(const float* __restrict__ dY, const float* __restrict__ X,
+                                                               float* __restrict__ Cp, int Mrows, int NI, int NJ, int chunk) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int l15 = lane & 15, q = lane >> 4;
+  const int i0 = blockIdx.y * 128 + (wid >> 1) * 64;
+  const int j0 = blockIdx.x * 128 + (wid & 1) * 64;
+  if (i0 >= NI || j0 >= NJ) return;
+  const int s = blockIdx.z;
+  const int mb = s * chunk, me = min(Mrows, mb + chunk);
+  f32x4 acc[4][4];
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) acc[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  const float* yp = dY + i0 + 4 * l15;
+  const float* xp = X + j0 + 4 * l15;
+  const int rlast = me > mb ? me - 1 : mb;
+  for (int m0 = mb; m0 < me; m0 += 32) {
+    f32x4 a4[8], b4[8];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {   // rows past the chunk end: clamped address, contribution zeroed
+      const int m = m0 + 8 * q + r;
+      const int rc = m < rlast ? m : rlast;
+      a4[r] = *reinterpret_cast<const f32x4*>(yp + (size_t)rc * NI) * ((m < me) ? 1.f : 0.f);
+      b4[r] = *reinterpret_cast<const f32x4*>(xp + (size_t)rc * NJ);
+    }
+    bf16x8 bh[4];
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb) {
+      const float x[8] = {b4[0][cb], b4[1][cb], b4[2][cb], b4[3][cb], b4[4][cb], b4[5][cb], b4[6][cb], b4[7][cb]};
+      bh[cb] = round_bf16x8(x);
+    }
+#pragma unroll
+    for (int ca = 0; ca < 4; ++ca) {
+      const float x[8] = {a4[0][ca], a4[1][ca], a4[2][ca], a4[3][ca], a4[4][ca], a4[5][ca], a4[6][ca], a4[7][ca]};
+      const bf16x8 ah = round_bf16x8(x);
+#pragma unroll
+      for (int cb = 0; cb < 4; ++cb) acc[ca][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh[cb], acc[ca][cb], 0, 0, 0);
+    }
+  }
+  float* cp = Cp + (size_t)s * NI * NJ;
+#pragma unroll
+  for (int ca = 0; ca < 4; ++ca)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int i = i0 + 4 * (q * 4 + r) + ca;
+      f32x4 v = {acc[ca][0][r], acc[ca][1][r], acc[ca][2][r], acc[ca][3][r]};
+      *reinterpret_cast<f32x4*>(cp + (size_t)i * NJ + j0 + 4 * l15) = v;
+    }
+}
+
 // LDS-staged version of the weight-gradient GEMM (NI, NJ multiples of 128): one workgroup = 128x128 outputs (4 waves of
 // 64x64 as above); operand slabs of 16 contraction rows (2 x 8 KB) travel by LDS-DMA through a 4-deep ring with counted
 // vmcnt waits, so ~3 slabs of loads are in flight per workgroup — the direct-load kernel above keeps a single wave per
@@ -1216,13 +1270,18 @@ __global__ __launch_bounds__(256) void gemm_f32_tn_kernel(const float* __restric
 // workgroups have 512 threads).  Same contraction order per output element either way.  `cpart` (optional): the
 // workgroups of feature-tile column 0 also emit the column sums of their dY rows (= this split's bias-gradient
 // partial, cpart[s * cstride + i]) from the fragments they read anyway.
-template <int NW, int NST>
+// BF = 1 (TSPO_SEL_BF16_MIXED): bf16 operands / fp32 accumulate, slabs of 32 contraction rows = one v_mfma_f32_16x16x32_bf16 k-step:
+// lane (l15, q) owns rows 8q..8q+7 (8 fragment reads per operand, rounded to bf16 in registers) - one MFMA per tile pair and slab where
+// the exact form issues eight.  The bias column sums (`cpart`) are taken from the fp32 values before the rounding.
+template <int NW, int NST, int BF = 0>
 __device__ __forceinline__ void gemm_f32_tn_lds_body(char* lds, const float* __restrict__ dY, const float* __restrict__ X,
                                                      float* __restrict__ Cp, float* __restrict__ cpart, int cstride,
                                                      int Mrows, int NI, int NJ, int chunk, int bj, int bi, int s) {
+  constexpr int ROWS = BF ? 32 : TN_ROWS;   // contraction rows per slab
+  constexpr int HALF = ROWS * 512;          // bytes of one operand's slab (rows of 128 floats)
   constexpr int WJ = NW / 2;            // waves along j
   constexpr int CB = 4 / (WJ / 2);      // interleaved 16-column tiles per wave along j: 4 (64 columns) or 2 (32 columns)
-  constexpr int PW = 8 / NW;            // DMA instructions per wave, operand and slab (2 rows each, 16 rows per slab)
+  constexpr int PW = ROWS / 2 / NW;     // DMA instructions per wave, operand and slab (2 rows each)
   typedef float fb_t __attribute__((ext_vector_type(CB)));
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int l15 = lane & 15, q = lane >> 4;
@@ -1236,7 +1295,7 @@ __device__ __forceinline__ void gemm_f32_tn_lds_body(char* lds, const float* __r
     for (int b = 0; b < CB; ++b) acc[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
   f32x4 csum = {0.f, 0.f, 0.f, 0.f};
   const bool want_cs = cpart != nullptr && bj == 0 && wj == 0;   // wave-uniform
-  const int nst = me > mb ? (me - mb + TN_ROWS - 1) / TN_ROWS : 0;
+  const int nst = me > mb ? (me - mb + ROWS - 1) / ROWS : 0;
   const int rlast = me > mb ? me - 1 : mb;
   const int prow = lane >> 5, pcol = (lane & 31) << 2;
   // NW = 8 reads its X fragments with ds_read_b64 (two 16-lane groups = rows m, m+1 per cycle, 512 B apart = the same banks):
@@ -1244,38 +1303,60 @@ __device__ __forceinline__ void gemm_f32_tn_lds_body(char* lds, const float* __r
   // were bank conflicts before, profiles/r4_h_policy_sq_counters.txt)
   const int pcolB = NW == 8 ? ((((lane & 31) >> 3) ^ prow) << 5) + ((lane & 7) << 2) : pcol;
   auto stage = [&](int t) {   // wave wid moves rows 2*PW*wid .. 2*PW*wid + 2*PW-1 of both slabs
-    char* buf = lds + (t % NST) * 16384;
+    char* buf = lds + (t % NST) * 2 * HALF;
 #pragma unroll
     for (int p = 0; p < PW; ++p) {
       const int rr = (wid * PW + p) * 2 + prow;
-      int r = mb + t * TN_ROWS + rr;
+      int r = mb + t * ROWS + rr;
       r = r < rlast ? r : rlast;
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(dY + (size_t)r * NI + i0 + pcol),
                                        (__attribute__((address_space(3))) void*)(buf + (wid * PW + p) * 1024), 16, 0, 0);
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(X + (size_t)r * NJ + j0 + pcolB),
-                                       (__attribute__((address_space(3))) void*)(buf + 8192 + (wid * PW + p) * 1024), 16, 0, 0);
+                                       (__attribute__((address_space(3))) void*)(buf + HALF + (wid * PW + p) * 1024), 16, 0, 0);
     }
   };
 #pragma unroll
   for (int t = 0; t < NST - 1; ++t)
     if (t < nst) stage(t);
   // (rows m = 4 ks + q: m & 1 = q & 1; slab rows rr = 2 * piece + prow: rr & 1 = prow)
-  const int offA = (wi * 64 + 4 * l15) * 4, offB = 8192 + ((NW == 8 ? (wj ^ (q & 1)) : wj) * 16 * CB + CB * l15) * 4;
+  const int offA = (wi * 64 + 4 * l15) * 4, offB = HALF + ((NW == 8 ? (wj ^ (q & 1)) : wj) * 16 * CB + CB * l15) * 4;
   for (int t = 0; t < nst; ++t) {
-    // slabs t+1, t+2 (2*PW DMA instructions each per wave) may stay in flight
+    // the newer slabs (2*PW DMA instructions each per wave) may stay in flight
     const int ahead = min(NST - 2, nst - 1 - t);
-    if (PW == 2) {
-      if (ahead >= 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-      else if (ahead == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    } else {
-      if (ahead >= 2) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-      else if (ahead == 1) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
+    const int cnt = ahead * 2 * PW;
+    if (cnt >= 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+    else if (cnt >= 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    else if (cnt >= 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();   // slab t visible to all waves; everyone is done with slab t-1 -> its slot is free
     if (t + NST - 1 < nst) stage(t + NST - 1);
-    const char* cur = lds + (t % NST) * 16384;
+    const char* cur = lds + (t % NST) * 2 * HALF;
+    if (BF) {
+      // rows m = 8q + r (m & 1 = r & 1), packed to bf16 pairs as soon as two are read (the fp32 fragments die early: the 8-wave form
+      // stays within the register budget of two workgroups per CU)
+      union { bf16x8 v; uint32_t u[4]; } ah[4], bh[CB];
+#pragma unroll
+      for (int r = 0; r < 8; r += 2) {
+        f32x4 a[2];
+        fb_t b[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const int m = 8 * q + r + h;
+          const float keep = (mb + t * ROWS + m < me) ? 1.f : 0.f;
+          a[h] = *reinterpret_cast<const f32x4*>(cur + offA + m * 512) * keep;
+          b[h] = *reinterpret_cast<const fb_t*>(cur + HALF + ((NW == 8 ? (wj ^ h) : wj) * 16 * CB + CB * l15) * 4 + m * 512);
+          if (want_cs) csum += a[h];
+        }
+#pragma unroll
+        for (int ca = 0; ca < 4; ++ca) ah[ca].u[r / 2] = pack_bf16x2(a[0][ca], a[1][ca]);
+#pragma unroll
+        for (int cb = 0; cb < CB; ++cb) bh[cb].u[r / 2] = pack_bf16x2(b[0][cb], b[1][cb]);
+      }
+#pragma unroll
+      for (int ca = 0; ca < 4; ++ca)
+#pragma unroll
+        for (int cb = 0; cb < CB; ++cb) acc[ca][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[ca].v, bh[cb].v, acc[ca][cb], 0, 0, 0);
+    } else {
 #pragma unroll
     for (int ks = 0; ks < TN_ROWS / 4; ++ks) {
       const int m = ks * 4 + q;
@@ -1287,6 +1368,7 @@ __device__ __forceinline__ void gemm_f32_tn_lds_body(char* lds, const float* __r
       for (int ca = 0; ca < 4; ++ca)
 #pragma unroll
         for (int cb = 0; cb < CB; ++cb) acc[ca][cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[ca], b[cb], acc[ca][cb], 0, 0, 0);
+    }
     }
   }
   float* cp = Cp + (size_t)s * NI * NJ;
@@ -1321,14 +1403,18 @@ __device__ __forceinline__ void gemm_f32_tn_lds_body(char* lds, const float* __r
 // form (plane s of Cp / cpart, reduced later).
 // LDS: row m of a slab = 64 floats (256 B = all 64 banks), so the two 16-lane groups a ds_read_b64 serves per cycle (rows m, m+1)
 // would hit the same banks: the DMA stores the 128-byte halves of odd rows swapped, the reads undo it.
-template <int NST, int KG>
+// BF = 1 (TSPO_SEL_BF16_MIXED): each K-group takes 32 rows of a 64-row step (ring stages of 2 x 16 KB) as one
+// v_mfma_f32_16x16x32_bf16 k-step - lane (l15, q) owns rows 8q..8q+7, operands rounded to bf16 in registers; fp32 column sums.
+template <int NST, int KG, int BF = 0>
 __device__ __forceinline__ void gemm_f32_tn64_body(char* lds, const float* __restrict__ dY, const float* __restrict__ X,
                                                    float* __restrict__ Cp, float* __restrict__ cpart, int cstride,
                                                    float* __restrict__ sq_partial, int accumulate, int Mrows, int NI, int NJ,
                                                    int chunk, int bj, int bi, int s, int wg_index) {
   // KG = 2: 8 waves; waves 4..7 (K-group 1) take rows 16..31 of every 32-row step and their accumulators are added to K-group 0's
   // through LDS at the end (fixed order): twice the waves per CU for the same tile count, half the dependent chain
-  constexpr int STEP = TN_ROWS * KG, SLAB = 8192 * KG;
+  constexpr int KROWS = BF ? 32 : TN_ROWS;        // contraction rows per K-group and step
+  constexpr int STEP = KROWS * KG, KSL = KROWS * 512, SLAB = KSL * KG;   // (KSL: one K-group's A | B rows of 256 B)
+  constexpr int PD = KROWS / 16;                  // DMA instructions per wave and operand (4 rows each)
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int kg = wid >> 2, w4 = wid & 3;
   const int l15 = lane & 15, q = lane >> 4;
@@ -1344,33 +1430,62 @@ __device__ __forceinline__ void gemm_f32_tn64_body(char* lds, const float* __res
   const bool want_cs = cpart != nullptr && bj == 0 && wj == 0;   // wave-uniform
   const int nst = me > mb ? (me - mb + STEP - 1) / STEP : 0;
   const int rlast = me > mb ? me - 1 : mb;
-  // DMA: wave w moves rows 4w..4w+3 of the step, both operands (one 1 KB piece each); lane (r4, chunk) fetches the 16 bytes whose LDS
-  // place is row r4, chunk `chunk`, i.e. source half (chunk >> 3) ^ (r4 & 1)
+  // DMA: wave w moves rows 4w..4w+3 of the step (BF: rows 8w..8w+7), both operands (one 1 KB piece each per 4 rows); lane (r4, chunk)
+  // fetches the 16 bytes whose LDS place is row r4, chunk `chunk`, i.e. source half (chunk >> 3) ^ (r4 & 1)
   const int r4 = lane >> 4, ch = lane & 15;
   const int scol = ((((ch >> 3) ^ (r4 & 1)) << 5) + ((ch & 7) << 2));
   auto stage = [&](int t) {
-    char* buf = lds + (t % NST) * SLAB + kg * 8192;
-    int r = mb + t * STEP + wid * 4 + r4;
-    r = r < rlast ? r : rlast;
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(dY + (size_t)r * NI + i0 + scol),
-                                     (__attribute__((address_space(3))) void*)(buf + w4 * 1024), 16, 0, 0);
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(X + (size_t)r * NJ + j0 + scol),
-                                     (__attribute__((address_space(3))) void*)(buf + 4096 + w4 * 1024), 16, 0, 0);
+    char* buf = lds + (t % NST) * SLAB + kg * KSL;
+#pragma unroll
+    for (int p = 0; p < PD; ++p) {
+      int r = mb + t * STEP + (wid * PD + p) * 4 + r4;
+      r = r < rlast ? r : rlast;
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(dY + (size_t)r * NI + i0 + scol),
+                                       (__attribute__((address_space(3))) void*)(buf + (w4 * PD + p) * 1024), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(X + (size_t)r * NJ + j0 + scol),
+                                       (__attribute__((address_space(3))) void*)(buf + KSL / 2 + (w4 * PD + p) * 1024), 16, 0, 0);
+    }
   };
 #pragma unroll
   for (int t = 0; t < NST - 1; ++t)
     if (t < nst) stage(t);
   // rows m = 4 ks + q: m & 1 = q & 1
-  const int offA = kg * 8192 + ((wi ^ (q & 1)) << 7) + l15 * 8, offB = kg * 8192 + 4096 + ((wj ^ (q & 1)) << 7) + l15 * 8;
+  const int offA = kg * KSL + ((wi ^ (q & 1)) << 7) + l15 * 8, offB = kg * KSL + KSL / 2 + ((wj ^ (q & 1)) << 7) + l15 * 8;
   for (int t = 0; t < nst; ++t) {
-    const int ahead = min(NST - 2, nst - 1 - t);   // newer steps of this wave (2 DMA instructions each) that may stay in flight
-    if (ahead >= 3) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    else if (ahead == 2) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else if (ahead == 1) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+    const int ahead = min(NST - 2, nst - 1 - t);   // newer steps of this wave (2 * PD DMA instructions each) that may stay in flight
+    const int cnt = ahead * 2 * PD;
+    if (cnt >= 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+    else if (cnt >= 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    else if (cnt >= 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();   // step t visible to all waves; everyone is done with step t-1 -> its slot is free
     if (t + NST - 1 < nst) stage(t + NST - 1);
     const char* cur = lds + (t % NST) * SLAB;
+    if (BF) {
+      // rows m = 8q + r (m & 1 = r & 1), packed to bf16 pairs as soon as two are read
+      union { bf16x8 v; uint32_t u[4]; } ah[2], bh[2];
+#pragma unroll
+      for (int r = 0; r < 8; r += 2) {
+        f32x2 a[2], b[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const int m = 8 * q + r + h;
+          const float keep = (mb + t * STEP + kg * KROWS + m < me) ? 1.f : 0.f;
+          a[h] = *reinterpret_cast<const f32x2*>(cur + kg * KSL + ((wi ^ h) << 7) + l15 * 8 + m * 256) * keep;
+          b[h] = *reinterpret_cast<const f32x2*>(cur + kg * KSL + KSL / 2 + ((wj ^ h) << 7) + l15 * 8 + m * 256);
+          if (want_cs) csum += a[h];
+        }
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+          ah[c].u[r / 2] = pack_bf16x2(a[0][c], a[1][c]);
+          bh[c].u[r / 2] = pack_bf16x2(b[0][c], b[1][c]);
+        }
+      }
+#pragma unroll
+      for (int ca = 0; ca < 2; ++ca)
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb) acc[ca][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[ca].v, bh[cb].v, acc[ca][cb], 0, 0, 0);
+    } else {
 #pragma unroll
     for (int ks = 0; ks < TN_ROWS / 4; ++ks) {
       const int m = ks * 4 + q;
@@ -1382,6 +1497,7 @@ __device__ __forceinline__ void gemm_f32_tn64_body(char* lds, const float* __res
       for (int ca = 0; ca < 2; ++ca)
 #pragma unroll
         for (int cb = 0; cb < 2; ++cb) acc[ca][cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[ca], b[cb], acc[ca][cb], 0, 0, 0);
+    }
     }
   }
   if (KG == 2) {   // K-group 1 -> LDS -> added by K-group 0 (18 floats per lane: 16 accumulators + 2 column sums)
@@ -1448,30 +1564,36 @@ __device__ __forceinline__ void gemm_f32_tn64_body(char* lds, const float* __res
   }
 }
 
+// (BF: a 2-deep ring of 64-row steps, 64 KB - the same rows in flight as the exact form's 3-deep ring of 32-row steps)
+template <int BF>
 __global__ __launch_bounds__(512) void gemm_f32_tn64_kernel(const float* __restrict__ dY, const float* __restrict__ X,
                                                             float* __restrict__ Cp, float* __restrict__ cpart, int cstride,
                                                             float* __restrict__ sq_partial, int accumulate, int Mrows, int NI,
                                                             int NJ, int chunk) {
-  __shared__ __attribute__((aligned(16))) char lds[3 * 16384];
+  __shared__ __attribute__((aligned(16))) char lds[BF ? 2 * 32768 : 3 * 16384];
   const int wg = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-  gemm_f32_tn64_body<3, 2>(lds, dY, X, Cp, cpart, cstride, sq_partial, accumulate, Mrows, NI, NJ, chunk, blockIdx.x, blockIdx.y,
-                           blockIdx.z, wg);
+  gemm_f32_tn64_body<BF ? 2 : 3, 2, BF>(lds, dY, X, Cp, cpart, cstride, sq_partial, accumulate, Mrows, NI, NJ, chunk, blockIdx.x,
+                                         blockIdx.y, blockIdx.z, wg);
 }
 
 // (3-deep ring here: 48 KB and <= 168 registers let three workgroups share a CU, so the 108 x S tiles of the q/k/v weight
 // gradient - 756 for BT = 2048 - are resident at once instead of leaving a half-empty second round)
-__global__ __launch_bounds__(256, 3) void gemm_f32_tn_lds_kernel(const float* __restrict__ dY, const float* __restrict__ X,
-                                                                 float* __restrict__ Cp, float* __restrict__ cpart,
-                                                                 int cstride, int Mrows, int NI, int NJ, int chunk) {
-  __shared__ __attribute__((aligned(16))) char lds[3 * 16384];   // per stage: A 16x512 B | B 16x512 B
-  gemm_f32_tn_lds_body<4, 3>(lds, dY, X, Cp, cpart, cstride, Mrows, NI, NJ, chunk, blockIdx.x, blockIdx.y, blockIdx.z);
+// BF: 32-row slabs (32 KB per stage) in a 2-deep ring, two workgroups per CU
+template <int BF>
+__global__ __launch_bounds__(256, BF ? 2 : 3) void gemm_f32_tn_lds_kernel(const float* __restrict__ dY, const float* __restrict__ X,
+                                                                         float* __restrict__ Cp, float* __restrict__ cpart,
+                                                                         int cstride, int Mrows, int NI, int NJ, int chunk) {
+  __shared__ __attribute__((aligned(16))) char lds[BF ? 2 * 32768 : 3 * 16384];   // per stage: A 16x512 B | B 16x512 B (BF: 32 rows)
+  gemm_f32_tn_lds_body<4, BF ? 2 : 3, BF>(lds, dY, X, Cp, cpart, cstride, Mrows, NI, NJ, chunk, blockIdx.x, blockIdx.y, blockIdx.z);
 }
 
 // One launch = the data-gradient GEMM of a linear layer (dX = dY W: the 64x96-tile kernel above, 512-thread workgroups)
 // AND the weight-gradient tiles of the layer after it (the two are independent).  Each alone fills the 256 CUs with one
 // workgroup per CU and leaves the matrix pipes idle across its barriers; the hardware dispatches the data-gradient
 // workgroups first and the weight-gradient ones into the second slot of every CU.
-template <int EPI>
+// BF (TSPO_SEL_BF16_MIXED): both halves take bf16 operands - the data gradient as the SPLIT = 2 form of the NT body, the weight-gradient
+// tiles as 32-row slabs in a 2-deep ring (the same 64 KB as the exact form's 4-deep ring of 16-row slabs).
+template <int EPI, int BF = 0>
 __global__ __launch_bounds__(512, 2) void dgrad_wgrad_kernel(const float* __restrict__ A, const float* __restrict__ W,
                                                             const float* __restrict__ R, float* __restrict__ C, int M,
                                                             int N, int K, int n_nt,
@@ -1483,16 +1605,17 @@ __global__ __launch_bounds__(512, 2) void dgrad_wgrad_kernel(const float* __rest
   const int b = blockIdx.x;
   if (b < n_nt) {
     const int nx = N / 96;
-    gemm_f32_nt_lds_body<EPI, 3, 4, 3, 0>(lds, A, W, nullptr, R, C, M, N, K, b % nx, b / nx);
+    gemm_f32_nt_lds_body<EPI, 3, 4, 3, BF ? 2 : 0>(lds, A, W, nullptr, R, C, M, N, K, b % nx, b / nx);
   } else {
     const int t = b - n_nt, tj = NJ >> 7, ti = NI >> 7;
-    gemm_f32_tn_lds_body<8, TN_NST>(lds, dY, X, Cp, cpart, cstride, M, NI, NJ, chunk, t % tj, (t / tj) % ti, t / (tj * ti));
+    gemm_f32_tn_lds_body<8, BF ? 2 : TN_NST, BF>(lds, dY, X, Cp, cpart, cstride, M, NI, NJ, chunk, t % tj, (t / tj) % ti,
+                                                t / (tj * ti));
   }
 }
 
 // Small-M form of the launch above (BT = 512: the 64x96 data-gradient tiling has 64 workgroups): 256-thread workgroups, the data
 // gradient in 32x32 tiles (gemm_f32_nt_lds_body<.., WN 1, NWM 2, ring 3, MI 1>), the weight-gradient tiles as four waves of 64x64.
-template <int EPI>
+template <int EPI, int BF = 0>
 __global__ __launch_bounds__(512) void dgrad_wgrad_small_kernel(const float* __restrict__ A, const float* __restrict__ W,
                                                                const float* __restrict__ R, float* __restrict__ C, int M,
                                                                int N, int K, int n_nt, int n_tiles,
@@ -1507,15 +1630,16 @@ __global__ __launch_bounds__(512) void dgrad_wgrad_small_kernel(const float* __r
   if (b < n_nt) {   // two 32x32 data-gradient tiles per workgroup (the last one may repeat a tile: same values written twice)
     const int half = threadIdx.x >> 8, nx = N / 32;
     const int tile = min(2 * b + half, n_tiles - 1);
-    gemm_f32_nt_lds_body<EPI, 1, 2, 3, 0, 1, 2>(lds + half * nt_lds_bytes<1, 3, 32>(), A, W, nullptr, R, C, M, N, K, tile % nx,
-                                                tile / nx);
+    gemm_f32_nt_lds_body<EPI, 1, 2, 3, BF ? 2 : 0, 1, 2>(lds + half * nt_lds_bytes<1, 3, 32>(), A, W, nullptr, R, C, M, N, K,
+                                                         tile % nx, tile / nx);
   } else if (t64) {   // 64x64 tiles, whole contraction per workgroup (or `chunk` rows of it): see gemm_f32_tn64_body
     const int t = b - n_nt, tj = NJ >> 6, ti = NI >> 6;
-    gemm_f32_tn64_body<3, 2>(lds, dY, X, Cp, cpart, cstride, sq_partial, accumulate, M, NI, NJ, chunk, t % tj, (t / tj) % ti,
-                             t / (tj * ti), t);
+    gemm_f32_tn64_body<BF ? 2 : 3, 2, BF>(lds, dY, X, Cp, cpart, cstride, sq_partial, accumulate, M, NI, NJ, chunk, t % tj,
+                                           (t / tj) % ti, t / (tj * ti), t);
   } else {
     const int t = b - n_nt, tj = NJ >> 7, ti = NI >> 7;
-    gemm_f32_tn_lds_body<8, TN_NST>(lds, dY, X, Cp, cpart, cstride, M, NI, NJ, chunk, t % tj, (t / tj) % ti, t / (tj * ti));
+    gemm_f32_tn_lds_body<8, BF ? 2 : TN_NST, BF>(lds, dY, X, Cp, cpart, cstride, M, NI, NJ, chunk, t % tj, (t / tj) % ti,
+                                                t / (tj * ti));
   }
 }
 
@@ -1764,10 +1888,13 @@ static int selector_forward_impl(const tspo_selector_weights* w, const float* im
                                  const float* clip, int B, int T, int D, int H, int M, int window, float tau,
                                  float* scores, float* temporal_attn, void* workspace, size_t workspace_bytes,
                                  tspo_stream_t stream, int flags) {
-  TSPO_REQUIRE((flags & ~(TSPO_SEL_BF16X3 | TSPO_SEL_BF16)) == 0, "selector_forward: unknown flags 0x%x", flags);
+  TSPO_REQUIRE((flags & ~(TSPO_SEL_BF16X3 | TSPO_SEL_BF16 | TSPO_SEL_BF16_MIXED)) == 0, "selector_forward: unknown flags 0x%x", flags);
   TSPO_REQUIRE((flags & (TSPO_SEL_BF16X3 | TSPO_SEL_BF16)) != (TSPO_SEL_BF16X3 | TSPO_SEL_BF16), "selector_forward: TSPO_SEL_BF16X3 and TSPO_SEL_BF16 are exclusive");
+  TSPO_REQUIRE(!(flags & TSPO_SEL_BF16_MIXED) || !(flags & (TSPO_SEL_BF16X3 | TSPO_SEL_BF16)),
+               "selector_forward: TSPO_SEL_BF16_MIXED is exclusive with TSPO_SEL_BF16X3 and TSPO_SEL_BF16");
   TSPO_REQUIRE(!(flags & TSPO_SEL_BF16) || D % 32 == 0, "selector_forward: TSPO_SEL_BF16 needs D %% 32 == 0 (D=%d)", D);
-  const int split = (flags & TSPO_SEL_BF16) ? 2 : ((flags & TSPO_SEL_BF16X3) ? 1 : 0);
+  // TSPO_SEL_BF16_MIXED: the forward arithmetic of TSPO_SEL_BF16 (bitwise the same scores), its workspace valid for a backward
+  const int split = (flags & (TSPO_SEL_BF16 | TSPO_SEL_BF16_MIXED)) ? 2 : ((flags & TSPO_SEL_BF16X3) ? 1 : 0);
   TSPO_REQUIRE(w && img && txt && scores && workspace, "selector_forward: null pointer");
   TSPO_REQUIRE(w->wqkv && w->bqkv && w->w1 && w->b1 && w->w2 && w->b2, "selector_forward: null weight pointer");
   if (int e = check_dims("selector_forward", B, T, D, H, M, window)) return e;
@@ -1820,26 +1947,35 @@ struct FinalGrad {
   float* sq = nullptr;     // one sum of squares per workgroup (or nullptr)
   int accumulate = 0;
 };
+// mode: 0 exact fp32, 1 bf16x3 (hi/lo split), 2 bf16 operands (TSPO_SEL_BF16_MIXED)
 int weight_grad(const float* dY, const float* X, float* part, float* cpart, int cstride, int BT, int NI, int NJ,
-                const SelWs& s, hipStream_t st, bool split, const FinalGrad& fin = FinalGrad()) {
+                const SelWs& s, hipStream_t st, int mode, const FinalGrad& fin = FinalGrad()) {
   if (fin.w) {
-    hipLaunchKernelGGL(gemm_f32_tn64_kernel, dim3(NJ / 64, NI / 64, 1), dim3(512), 0, st, dY, X, fin.w, fin.b, 0, fin.sq,
-                       fin.accumulate, BT, NI, NJ, (BT + 3) / 4 * 4);
+    if (mode == 2)
+      hipLaunchKernelGGL(gemm_f32_tn64_kernel<1>, dim3(NJ / 64, NI / 64, 1), dim3(512), 0, st, dY, X, fin.w, fin.b, 0, fin.sq,
+                         fin.accumulate, BT, NI, NJ, (BT + 3) / 4 * 4);
+    else
+      hipLaunchKernelGGL(gemm_f32_tn64_kernel<0>, dim3(NJ / 64, NI / 64, 1), dim3(512), 0, st, dY, X, fin.w, fin.b, 0, fin.sq,
+                         fin.accumulate, BT, NI, NJ, (BT + 3) / 4 * 4);
     return tspo::check_launch("selector weight_grad (64x64, final)");
   }
   const int chunk = ((BT + s.S - 1) / s.S + 3) / 4 * 4;
   dim3 grid((NJ + 127) / 128, (NI + 127) / 128, s.S);
-  if (split && NI % 128 == 0 && NJ % 128 == 0)
+  if (mode == 1 && NI % 128 == 0 && NJ % 128 == 0)
     hipLaunchKernelGGL(gemm_f32_tn_split_kernel, grid, dim3(256), 0, st, dY, X, part, BT, NI, NJ, chunk);
+  else if (mode == 2 && NI % 128 == 0 && NJ % 128 == 0)
+    hipLaunchKernelGGL(gemm_f32_tn_lds_kernel<1>, grid, dim3(256), 0, st, dY, X, part, cpart, cstride, BT, NI, NJ, chunk);
+  else if (mode == 2)
+    hipLaunchKernelGGL(gemm_f32_tn_bf16_kernel, grid, dim3(256), 0, st, dY, X, part, BT, NI, NJ, chunk);
   else if (NI % 128 == 0 && NJ % 128 == 0)
-    hipLaunchKernelGGL(gemm_f32_tn_lds_kernel, grid, dim3(256), 0, st, dY, X, part, cpart, cstride, BT, NI, NJ, chunk);
+    hipLaunchKernelGGL(gemm_f32_tn_lds_kernel<0>, grid, dim3(256), 0, st, dY, X, part, cpart, cstride, BT, NI, NJ, chunk);
   else
     hipLaunchKernelGGL(gemm_f32_tn_kernel, grid, dim3(256), 0, st, dY, X, part, BT, NI, NJ, chunk);
   return tspo::check_launch("selector weight_grad");
 }
 
 // dX = mask?(dY W) together with the weight gradient dYw^T Xw of another layer in one launch (see dgrad_wgrad_kernel)
-template <int EPI>
+template <int EPI, int BF>
 int dgrad_with_wgrad(const float* dY, const float* Wt, const float* R, float* dX, int BT, int N, int K, const float* dYw,
                      const float* Xw, float* part, float* cpart, int cstride, int NI, int NJ, const SelWs& s,
                      hipStream_t st, const FinalGrad& fin = FinalGrad()) {
@@ -1852,14 +1988,14 @@ int dgrad_with_wgrad(const float* dY, const float* Wt, const float* R, float* dX
   if (n_nt < 128 && N % 32 == 0) {
     const int n_tiles = (N / 32) * ((BT + 31) / 32), n_nt_s = (n_tiles + 1) / 2;
     if (fin.w)
-      hipLaunchKernelGGL((dgrad_wgrad_small_kernel<EPI>), dim3(n_nt_s + (NI / 64) * (NJ / 64)), dim3(512), 0, st, dY, Wt, R, dX, BT, N,
+      hipLaunchKernelGGL((dgrad_wgrad_small_kernel<EPI, BF>), dim3(n_nt_s + (NI / 64) * (NJ / 64)), dim3(512), 0, st, dY, Wt, R, dX, BT, N,
                          K, n_nt_s, n_tiles, dYw, Xw, fin.w, fin.b, 0, NI, NJ, (BT + 3) / 4 * 4, 1, fin.sq, fin.accumulate);
     else
-      hipLaunchKernelGGL((dgrad_wgrad_small_kernel<EPI>), dim3(n_nt_s + n_tn), dim3(512), 0, st, dY, Wt, R, dX, BT, N, K, n_nt_s,
+      hipLaunchKernelGGL((dgrad_wgrad_small_kernel<EPI, BF>), dim3(n_nt_s + n_tn), dim3(512), 0, st, dY, Wt, R, dX, BT, N, K, n_nt_s,
                          n_tiles, dYw, Xw, part, cpart, cstride, NI, NJ, chunk, 0, (float*)nullptr, 0);
     return tspo::check_launch("selector dgrad+wgrad");
   }
-  hipLaunchKernelGGL((dgrad_wgrad_kernel<EPI>), dim3(n_nt + n_tn), dim3(512), 0, st, dY, Wt, R, dX, BT, N, K, n_nt, dYw, Xw,
+  hipLaunchKernelGGL((dgrad_wgrad_kernel<EPI, BF>), dim3(n_nt + n_tn), dim3(512), 0, st, dY, Wt, R, dX, BT, N, K, n_nt, dYw, Xw,
                      part, cpart, cstride, NI, NJ, chunk);
   return tspo::check_launch("selector dgrad+wgrad");
 }
@@ -1870,9 +2006,13 @@ static int selector_backward_impl(const tspo_selector_weights* w, const float* i
                                   const tspo_selector_grads* g, void* workspace, size_t workspace_bytes,
                                   tspo_stream_t stream, int flags, const PgIn* pg = nullptr, float* norm_partials = nullptr,
                                   int* n_partials = nullptr) {
-  const bool split = (flags & TSPO_SEL_BF16X3) != 0;
   const int accum = (flags & TSPO_SEL_ACCUMULATE) ? 1 : 0;
-  TSPO_REQUIRE((flags & ~(TSPO_SEL_BF16X3 | TSPO_SEL_ACCUMULATE)) == 0, "selector_backward: unknown flags 0x%x", flags);
+  TSPO_REQUIRE((flags & ~(TSPO_SEL_BF16X3 | TSPO_SEL_ACCUMULATE | TSPO_SEL_BF16_MIXED)) == 0, "selector_backward: unknown flags 0x%x",
+               flags);
+  TSPO_REQUIRE((flags & (TSPO_SEL_BF16X3 | TSPO_SEL_BF16_MIXED)) != (TSPO_SEL_BF16X3 | TSPO_SEL_BF16_MIXED),
+               "selector_backward: TSPO_SEL_BF16X3 and TSPO_SEL_BF16_MIXED are exclusive");
+  // 0 exact fp32, 1 bf16x3, 2 bf16 operands (the weight-gradient and data-gradient GEMMs of TSPO_SEL_BF16_MIXED)
+  const int mode = (flags & TSPO_SEL_BF16_MIXED) ? 2 : ((flags & TSPO_SEL_BF16X3) ? 1 : 0);
   TSPO_REQUIRE(w && img && txt && (dscores || pg) && g && workspace, "selector_backward: null pointer");
   TSPO_REQUIRE(g->wqkv && g->bqkv && g->w1 && g->b1 && g->w2 && g->b2, "selector_backward: null grad pointer");
   if (int e = check_dims("selector_backward", B, T, D, H, M, window)) return e;
@@ -1893,9 +2033,9 @@ static int selector_backward_impl(const tspo_selector_weights* w, const float* i
   else
     hipLaunchKernelGGL(score_bwd_kernel<false>, dim3(n_score + 2 * tpr * tpr), dim3(256), 0, st, s.h2, txt, dscores, s.dh2, B,
                        T, D, M, tau, n_score, w->w1, s.w1t, w->w2, s.w2t, PgIn{});
-  // exact-fp32 path with 128-divisible D: bias-gradient column sums come out of the weight-gradient kernels, and each of
-  // the two DxD weight gradients shares a launch with the data-gradient GEMM that does not depend on it
-  const bool fused = !split && D % 128 == 0 && D % 96 == 0;
+  // exact-fp32 (and bf16-operand) path with 128-divisible D: bias-gradient column sums come out of the weight-gradient kernels, and
+  // each of the two DxD weight gradients shares a launch with the data-gradient GEMM that does not depend on it
+  const bool fused = mode != 1 && D % 128 == 0 && D % 96 == 0;
   const int cstride = 5 * D;
   // short contractions (the small-M forms: BT = 512, the reference's micro-batch): 64x64 weight-gradient tiles that hold the whole
   // contraction write the FINAL gradients (and their sums of squares) - no partial planes, no reduction launch
@@ -1909,18 +2049,25 @@ static int selector_backward_impl(const tspo_selector_weights* w, const float* i
   }
   if (fused) {
     // mlp.2 data gradient (dh1) || mlp.2 weight gradient (dh2^T h1)
-    if (int e = dgrad_with_wgrad<EPI_MASK>(s.dh2, s.w2t, s.h1, s.dh1, BT, D, D, s.dh2, s.h1, part_w2, s.cpart, cstride, D, D, s,
-                                           st, f2)) return e;
-    // mlp.0 data gradient (dctx) || mlp.0 weight gradient (dh1^T ctx)
-    if (int e = dgrad_with_wgrad<EPI_NONE>(s.dh1, s.w1t, nullptr, s.dctx, BT, D, D, s.dh1, s.ctx, part_w1, s.cpart + D, cstride,
-                                           D, D, s, st, f1)) return e;
+    if (mode == 2) {
+      if (int e = dgrad_with_wgrad<EPI_MASK, 1>(s.dh2, s.w2t, s.h1, s.dh1, BT, D, D, s.dh2, s.h1, part_w2, s.cpart, cstride, D, D, s,
+                                                st, f2)) return e;
+      if (int e = dgrad_with_wgrad<EPI_NONE, 1>(s.dh1, s.w1t, nullptr, s.dctx, BT, D, D, s.dh1, s.ctx, part_w1, s.cpart + D,
+                                                cstride, D, D, s, st, f1)) return e;
+    } else {
+      if (int e = dgrad_with_wgrad<EPI_MASK, 0>(s.dh2, s.w2t, s.h1, s.dh1, BT, D, D, s.dh2, s.h1, part_w2, s.cpart, cstride, D, D, s,
+                                                st, f2)) return e;
+      // mlp.0 data gradient (dctx) || mlp.0 weight gradient (dh1^T ctx)
+      if (int e = dgrad_with_wgrad<EPI_NONE, 0>(s.dh1, s.w1t, nullptr, s.dctx, BT, D, D, s.dh1, s.ctx, part_w1, s.cpart + D,
+                                                cstride, D, D, s, st, f1)) return e;
+    }
   } else {
     // mlp.2
-    if (int e = weight_grad(s.dh2, s.h1, part_w2, nullptr, 0, BT, D, D, s, st, split)) return e;
-    if (int e = launch_gemm_nt<EPI_MASK>(s.dh2, s.w2t, nullptr, s.h1, s.dh1, BT, D, D, st, split)) return e;
+    if (int e = weight_grad(s.dh2, s.h1, part_w2, nullptr, 0, BT, D, D, s, st, mode)) return e;
+    if (int e = launch_gemm_nt<EPI_MASK>(s.dh2, s.w2t, nullptr, s.h1, s.dh1, BT, D, D, st, mode)) return e;
     // mlp.0
-    if (int e = weight_grad(s.dh1, s.ctx, part_w1, nullptr, 0, BT, D, D, s, st, split)) return e;
-    if (int e = launch_gemm_nt<EPI_NONE>(s.dh1, s.w1t, nullptr, nullptr, s.dctx, BT, D, D, st, split)) return e;
+    if (int e = weight_grad(s.dh1, s.ctx, part_w1, nullptr, 0, BT, D, D, s, st, mode)) return e;
+    if (int e = launch_gemm_nt<EPI_NONE>(s.dh1, s.w1t, nullptr, nullptr, s.dctx, BT, D, D, st, mode)) return e;
   }
   // banded attention
   const long pairs = (long)BT * H;
@@ -1932,7 +2079,7 @@ static int selector_backward_impl(const tspo_selector_weights* w, const float* i
     hipLaunchKernelGGL(band_attn_bwd_kv_kernel, dim3(pb), dim3(256), 0, st, s.qkv, s.P, s.dS, s.dctx, s.dqkv, B, T, D, H,
                        window);
   // q/k/v projections
-  if (int e = weight_grad(s.dqkv, s.xpe, part_qkv, fused ? s.cpart + 2 * D : nullptr, cstride, BT, 3 * D, D, s, st, split, fq))
+  if (int e = weight_grad(s.dqkv, s.xpe, part_qkv, fused ? s.cpart + 2 * D : nullptr, cstride, BT, 3 * D, D, s, st, mode, fq))
     return e;
   if (t64) {   // every gradient is final
     if (norm_partials && n_partials) *n_partials = 5 * t64_tiles;
@@ -1971,6 +2118,15 @@ static int selector_backward_impl(const tspo_selector_weights* w, const float* i
   hipLaunchKernelGGL(reduce_segments_kernel, dim3(nb), dim3(256), 0, st, L, norm_partials, accum);
   (void)img;
   return tspo::check_launch("selector_backward");
+}
+
+extern "C" int tspo_selector_supported_flags(int entry) {
+  switch (entry) {   // (host only: no device is touched)
+    case 0: return TSPO_SEL_BF16X3 | TSPO_SEL_BF16 | TSPO_SEL_BF16_MIXED;
+    case 1:
+    case 2: return TSPO_SEL_BF16X3 | TSPO_SEL_ACCUMULATE | TSPO_SEL_BF16_MIXED;
+    default: return tspo::set_err(TSPO_EINVAL, "selector_supported_flags: entry %d (0 forward_ex, 1 backward_ex, 2 policy_backward)", entry);
+  }
 }
 
 extern "C" int tspo_policy_backward(const tspo_selector_weights* w, const float* img, const float* txt, const float* rewards,

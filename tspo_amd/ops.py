@@ -206,6 +206,8 @@ def selector_workspace(B, T, D, H, M, window, device) -> torch.Tensor:
 SEL_BF16X3 = 1       # include/tspo_hip.h: TSPO_SEL_BF16X3
 SEL_ACCUMULATE = 2   # include/tspo_hip.h: TSPO_SEL_ACCUMULATE (backward calls: add to the gradient buffers)
 SEL_BF16 = 4         # include/tspo_hip.h: TSPO_SEL_BF16 (forward only: bf16 GEMM operands, fp32 accumulate - the reference's inference precision)
+SEL_BF16_MIXED = 8   # include/tspo_hip.h: TSPO_SEL_BF16_MIXED (forward + backward: bf16 GEMM operands, fp32 accumulate - the reference's bf16 training)
+SEL_PRECISIONS = ("fp32", "bf16x3", "bf16_mixed")   # training (forward + backward); "bf16" is forward / inference only
 
 
 def _sel_flags(precision: str, accumulate: bool = False, forward: bool = False) -> int:
@@ -214,9 +216,11 @@ def _sel_flags(precision: str, accumulate: bool = False, forward: bool = False) 
         return acc
     if precision == "bf16x3":
         return SEL_BF16X3 | acc
+    if precision == "bf16_mixed":
+        return SEL_BF16_MIXED | acc
     if precision == "bf16" and forward:
         return SEL_BF16
-    raise ValueError(f"selector precision must be 'fp32' or 'bf16x3' (forward / inference also 'bf16'), got {precision!r}")
+    raise ValueError(f"selector precision must be 'fp32', 'bf16x3' or 'bf16_mixed' (forward / inference also 'bf16'), got {precision!r}")
 
 
 def selector_forward(flat: torch.Tensor, img: torch.Tensor, txt: torch.Tensor, clip: Optional[torch.Tensor],
@@ -226,7 +230,9 @@ def selector_forward(flat: torch.Tensor, img: torch.Tensor, txt: torch.Tensor, c
     (scores [B,T] f32, temporal_attn [B,T,D] f32 | None, workspace).
     precision="bf16x3" (opt-in, training): split-precision GEMMs on the bf16 MFMA, ~1e-5 relative error.
     precision="bf16" (opt-in, inference): the reference's own inference precision (gen_id_tspo.py:55) - GEMM operands rounded to
-    bf16, fp32 accumulation, fp32 between the GEMMs; a workspace written by it is NOT valid for a backward."""
+    bf16, fp32 accumulation, fp32 between the GEMMs; a workspace written by it is NOT valid for a backward.
+    precision="bf16_mixed" (opt-in, training): the same forward arithmetic as "bf16" (bitwise the same scores), for a backward with
+    precision="bf16_mixed" (bf16 operands in the five backward GEMMs too, the reference's `--bf16` training)."""
     _need_gpu(flat, img, txt, clip)
     assert flat.dtype == torch.float32 and flat.is_contiguous()
     x, e = _f32c(img), _f32c(txt)
@@ -247,7 +253,7 @@ def selector_forward(flat: torch.Tensor, img: torch.Tensor, txt: torch.Tensor, c
 def selector_backward(flat: torch.Tensor, flat_grad: torch.Tensor, img, txt, dscores, H, window, tau, ws,
                       precision: str = "fp32", accumulate: bool = False):
     """Writes the gradient of every trainable tensor into `flat_grad` (same layout as `flat`); accumulate=True ADDS it to what
-    `flat_grad` holds (gradient accumulation without a scratch bucket)."""
+    `flat_grad` holds (gradient accumulation without a scratch bucket).  `precision` must be the one of the forward that wrote `ws`."""
     _need_gpu(flat, flat_grad, img, txt, dscores, ws)
     x, e, d = _f32c(img), _f32c(txt), _f32c(dscores)
     B, T, D = x.shape

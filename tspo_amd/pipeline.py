@@ -72,15 +72,17 @@ class RolloutContext:
     """What `PolicyTrainer.rollout` saved for the matching backward: the selector workspace holding the activations
     of THAT forward, the shapes / temperature they belong to, and the parameter version they were computed with.
     Opaque to callers; `PolicyTrainer.backward` validates and consumes it (a context is good for one backward)."""
-    __slots__ = ("ws", "shape", "M", "tau", "param_version", "serial", "consumed", "owner", "idx", "idx_version", "micro_steps")
+    __slots__ = ("ws", "shape", "M", "tau", "param_version", "serial", "consumed", "owner", "idx", "idx_version", "micro_steps",
+                 "precision")
 
-    def __init__(self, ws, shape, M, tau, param_version, serial, owner, idx=None, micro_steps=1):
+    def __init__(self, ws, shape, M, tau, param_version, serial, owner, idx=None, micro_steps=1, precision="fp32"):
         self.ws, self.shape, self.M, self.tau = ws, tuple(shape), M, float(tau)
         self.param_version, self.serial, self.consumed, self.owner = param_version, serial, False, owner
         # the index tensor this rollout emitted (ascending by construction) - the TENSOR, which also pins its storage, and its
         # version counter: an address can be recycled by the allocator and `idx.copy_(...)` keeps it, identity + version cannot lie
         self.idx, self.idx_version = idx, (idx._version if idx is not None else -1)
         self.micro_steps = int(micro_steps)  # how many micro-steps of the accumulation window this batch holds
+        self.precision = precision           # GEMM precision of the forward that wrote `ws` (its backward must use the same)
 
 
 class PolicyTrainer:
@@ -108,8 +110,9 @@ class PolicyTrainer:
                  max_grad_norm: float = 1.0, seed: int = 2024, process_group=None, gemm_precision: str = "fp32",
                  grad_accum_steps: int = 1, lr_schedule: Optional[Callable[[int], float]] = None,
                  reduce_fn: Optional[Callable] = None, rank: Optional[int] = None):
-        # gemm_precision: "fp32" (exact fp32 MFMA, default) or "bf16x3" (opt-in split-precision GEMMs, ~1e-5 relative
-        # error; the reference trains in bf16, train_deepspeed.sh:33)
+        # gemm_precision: "fp32" (exact fp32 MFMA, default), "bf16x3" (opt-in split-precision GEMMs, ~1e-5 relative error) or
+        # "bf16_mixed" (opt-in: bf16 GEMM operands with fp32 accumulation in the forward and the backward, fp32 everywhere else -
+        # the reference's own training precision, `--bf16` with fp32 master weights, train_deepspeed.sh:33-34)
         ops._sel_flags(gemm_precision)
         self.gemm_precision = gemm_precision
         self.flat = flat
@@ -183,7 +186,8 @@ class PolicyTrainer:
                                             ws=ws, precision=self.gemm_precision)
         out = ops.gumbel_topk(scores, k, G, noise=noise, seed=self._rank_seed(), offset=self._rollouts,
                               prompts_per_offset=B // n if n > 1 else 0)
-        ctx = RolloutContext(ws, (B, T, D), txt.shape[1], tau, self._param_version, self._rollouts, self, out["idx"], n)
+        ctx = RolloutContext(ws, (B, T, D), txt.shape[1], tau, self._param_version, self._rollouts, self, out["idx"], n,
+                             precision=self.gemm_precision)
         self._rollouts += n
         return scores, out["idx"], out["logp"], ctx
 
@@ -196,6 +200,10 @@ class PolicyTrainer:
             raise RuntimeError("this RolloutContext was already used by a backward(); call rollout() again")
         if ctx.param_version != self._param_version:
             raise RuntimeError("stale RolloutContext: the parameters changed (optimizer_step) after its rollout()")
+        if ctx.precision != self.gemm_precision:
+            # the workspace holds what a forward of ctx.precision saved; the library keeps no state and cannot tell
+            raise RuntimeError(f"backward(): gemm_precision changed from {ctx.precision!r} (the rollout) to {self.gemm_precision!r}; "
+                               "call rollout() again")
         if tuple(feats.shape) != ctx.shape or txt.shape[1] != ctx.M:
             raise ValueError(f"backward(): feats {tuple(feats.shape)} / txt M={txt.shape[1]} do not match the rollout "
                              f"this context belongs to ({ctx.shape}, M={ctx.M})")

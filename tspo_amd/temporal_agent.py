@@ -55,8 +55,9 @@ class _SelectorFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, module, img, txt, clip, window, tau, *params):
         flat = module._flat_params(training=True)   # (grad mode is off inside Function.forward; this IS the training path)
-        scores, attn, ws = ops.selector_forward(flat, img, txt, clip, module.num_heads, window, tau)
-        ctx.module, ctx.window, ctx.tau, ctx.ws = module, window, tau, ws
+        prec = module.training_gemm_precision
+        scores, attn, ws = ops.selector_forward(flat, img, txt, clip, module.num_heads, window, tau, precision=prec)
+        ctx.module, ctx.window, ctx.tau, ctx.ws, ctx.precision = module, window, tau, ws, prec
         ctx.save_for_backward(img, txt)
         # the backward needs the weights THIS forward used.  Packed copy of non-flat parameters: it is repacked in place on
         # the next forward, so this graph keeps a private copy (14 MB).  Flat mode: the live bucket is used and its
@@ -77,7 +78,8 @@ class _SelectorFn(torch.autograd.Function):
             raise RuntimeError("MultiModal_Align: the flat parameter bucket was modified in place between this forward and "
                                "its backward (optimizer step / EMA swap with a graph still alive); run the forward again")
         fg = torch.zeros_like(ctx.flat)
-        ops.selector_backward(ctx.flat, fg, img, txt, dscores.contiguous(), m.num_heads, ctx.window, ctx.tau, ctx.ws)
+        ops.selector_backward(ctx.flat, fg, img, txt, dscores.contiguous(), m.num_heads, ctx.window, ctx.tau, ctx.ws,
+                              precision=ctx.precision)
         offs = ops.flat_offsets(m.dim)
         grads = []
         for name, p in m._trainable_named():
@@ -105,8 +107,12 @@ class MultiModal_Align(nn.Module):
         # inference-time GEMM precision (not a constructor argument: the reference's signature stays): "fp32" (default - exact fp32
         # MFMA on the parameter VALUES, the mode of every greedy-index parity claim) or "bf16" (the reference's own inference
         # precision, gen_id_tspo.py:55: bf16 GEMM operands, fp32 accumulation - ops.selector_forward(precision="bf16")).
-        # Training (grad mode) always runs exact fp32 unless PolicyTrainer(gemm_precision="bf16x3") is used.
+        # Training (grad mode) has its own attribute, training_gemm_precision: "fp32" (default, exact) or "bf16_mixed" (the
+        # reference's `--bf16` training, train_deepspeed.sh:33-34: bf16 GEMM operands with fp32 accumulation in the forward and
+        # the backward - ops.selector_backward(precision="bf16_mixed")); "bf16x3" is accepted too.  The mode a forward used is
+        # stored with its graph, so its backward runs in the same mode.  PolicyTrainer(gemm_precision=...) is the fused path.
         self.inference_gemm_precision = "fp32"
+        self.training_gemm_precision = "fp32"
         self._cache_key = None
         self._cache_flat = None
 
