@@ -196,6 +196,29 @@ def test_attention_kernel_register_audit(tmp_path):
     assert sorted(scratch) in ([], ["scratch_load_dword", "scratch_store_dword"]), scratch      # one store + one reload per item, or none
 
 
+def test_selector_kernel_register_audit(tmp_path):
+    """Every kernel of selector.hip runs without scratch or spills; the bf16-operand data+weight-gradient launches
+    (dgrad_wgrad_kernel / dgrad_wgrad_small_kernel, Prec = PREC_BF16) keep two 512-thread workgroups per CU (VGPRs + AGPRs <= 128);
+    and the GEMM precision stays one template parameter - no per-precision duplicate or unreachable kernels (<= 112 symbols)."""
+    import subprocess
+    from tspo_amd import build as b
+    asm = tmp_path / "selector.s"
+    subprocess.check_call([b._hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only", "-S",
+                           os.path.join(b.CSRC, "selector.hip"), "-o", str(asm)])
+    kernels = {}
+    for md in re.findall(r"\n  - (\.agpr_count:.*?\.wavefront_size)", open(asm).read(), flags=re.S):
+        kernels[re.search(r"\.name:\s+(\S+)", md).group(1)] = {k: int(re.search(r"\." + k + r":\s+(\d+)", md).group(1)) for k in
+                                                               ("agpr_count", "vgpr_count", "private_segment_fixed_size",
+                                                                "vgpr_spill_count", "sgpr_spill_count")}
+    assert 0 < len(kernels) <= 112, len(kernels)
+    for name, v in kernels.items():
+        assert v["private_segment_fixed_size"] == 0 and v["vgpr_spill_count"] == 0 and v["sgpr_spill_count"] == 0, (name, v)
+    bf16_fused = {n: v for n, v in kernels.items() if re.search(r"dgrad_wgrad(_small)?_kernel\w*PrecE2E", n)}
+    assert len(bf16_fused) == 4, sorted(kernels)
+    for name, v in bf16_fused.items():
+        assert v["vgpr_count"] + v["agpr_count"] <= 128, (name, v)
+
+
 def test_build_names_the_validated_toolchain():
     """the wait states around the inline-asm MFMAs were validated with ONE compiler; building with another, or with
     extra flags, must say so and name the post-build checks (it is not an error)."""

@@ -7,39 +7,61 @@
 // L2/Infinity-Cache resident, an LDS round trip would be pure overhead).  The
 // windowed attention is a banded kernel: O(T*w) work, the T x T mask and
 // score tensors of the reference (temporal_agent.py:40-51, 97-104) never exist.
+#include <type_traits>
+
 #include "common.h"
 
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(2))) float f32x2;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 
-// Split-precision operands ("bf16x3"): x = hi + lo + O(2^-17 |x|) with hi = bf16(x), lo = bf16(x - hi); a product is
-// taken as hi*hi + hi*lo + lo*hi on the bf16 MFMA (fp32 accumulate), dropping only lo*lo ~ 2^-16 relative.  Optional
-// mode of the selector GEMMs for training (TSPO_SEL_BF16X3): ~1e-5 relative error instead of fp32's ~1e-6, far inside
-// the bf16 autocast the reference trains with, at several times the fp32-MFMA rate.
-__device__ __forceinline__ void split_bf16x8(const float (&x)[8], bf16x8& hi, bf16x8& lo) {
-  union { bf16x8 v; uint32_t u[4]; } h, l;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    h.u[j] = pack_bf16x2(x[2 * j], x[2 * j + 1]);
-    const float r0 = x[2 * j] - __uint_as_float(h.u[j] << 16);
-    const float r1 = x[2 * j + 1] - __uint_as_float(h.u[j] & 0xffff0000u);
-    l.u[j] = pack_bf16x2(r0, r1);
-  }
-  hi = h.v;
-  lo = l.v;
-}
-
-// bf16 operands, fp32 accumulation (TSPO_SEL_BF16, inference): the operand rounded to nearest-even bf16 - what a bf16 model holds
-// (gen_id_tspo.py:55) - one MFMA per 32-deep slab; products of bf16 values are exact in the fp32 accumulator.
-__device__ __forceinline__ bf16x8 round_bf16x8(const float (&x)[8]) {
-  union { bf16x8 v; uint32_t u[4]; } h;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) h.u[j] = pack_bf16x2(x[2 * j], x[2 * j + 1]);
-  return h.v;
-}
-
 namespace {
+
+// Operand precision of the selector GEMMs: decoded from the flags once (sel_prec), the template parameter of every GEMM.
+// PREC_F32: exact fp32 (v_mfma_f32_16x16x4_f32), the default.  PREC_BF16X3 (TSPO_SEL_BF16X3): x = hi + lo + O(2^-17 |x|) with
+// hi = bf16(x), lo = bf16(x - hi), products lo*hi + hi*lo + hi*hi on the bf16 MFMA (fp32 accumulate), dropping only lo*lo:
+// ~1e-5 relative error instead of fp32's ~1e-6, at several times the fp32-MFMA rate.  PREC_BF16 (TSPO_SEL_BF16, _BF16_MIXED):
+// operands rounded to nearest-even bf16 - what a bf16 model holds (gen_id_tspo.py:55) - whose products are exact in fp32.
+// Both bf16 precisions share one k-step: a lane's 8 values of a 32-deep slab are one operand of v_mfma_f32_16x16x32_bf16 (BfOp,
+// packed by bf_pack, multiplied by bf_mfma); the fp32 precision keeps its own 16x16x4 k-step in each body.
+enum Prec { PREC_F32 = 0, PREC_BF16X3 = 1, PREC_BF16 = 2 };
+
+union bf16x8u {
+  bf16x8 v;
+  uint32_t u[4];
+};
+template <Prec P>
+struct BfOp {   // PREC_BF16: the rounded values
+  bf16x8u hi;
+};
+template <>
+struct BfOp<PREC_BF16X3> {
+  bf16x8u hi, lo;
+};
+
+// contraction values 2j, 2j+1 of the operand (pairs are packed as soon as they are read: the fp32 fragments die early)
+template <Prec P>
+__device__ __forceinline__ void bf_pack(BfOp<P>& o, int j, float x0, float x1) {
+  o.hi.u[j] = pack_bf16x2(x0, x1);
+  if constexpr (P == PREC_BF16X3)
+    o.lo.u[j] = pack_bf16x2(x0 - __uint_as_float(o.hi.u[j] << 16), x1 - __uint_as_float(o.hi.u[j] & 0xffff0000u));
+}
+
+// all 8 contraction values of the operand
+template <Prec P>
+__device__ __forceinline__ void bf_pack8(BfOp<P>& o, const float (&x)[8]) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) bf_pack(o, j, x[2 * j], x[2 * j + 1]);
+}
+
+template <Prec P>
+__device__ __forceinline__ f32x4 bf_mfma(const BfOp<P>& a, const BfOp<P>& b, f32x4 acc) {
+  if constexpr (P == PREC_BF16X3) {
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.lo.v, b.hi.v, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.hi.v, b.lo.v, acc, 0, 0, 0);
+  }
+  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.hi.v, b.hi.v, acc, 0, 0, 0);
+}
 
 // ---------------------------------------------------------------------------
 // x_pe = x + pe, pe[t,2i] = sin((t/T) * exp(2i * -ln(1e4)/C)), pe[t,2i+1] = cos(..)
@@ -66,94 +88,12 @@ __global__ __launch_bounds__(256) void posenc_add_kernel(const float* __restrict
 
 // ---------------------------------------------------------------------------
 // C[M,N] = A[M,K] * W[N,K]^T (+ bias[N]) with optional ReLU / residual add /
-// relu-mask multiply.  One wave = 32x32 outputs (2x2 MFMA tiles), 4 waves =
-// 64x64 per workgroup.  K % 16 == 0, N % 64 == 0, rows clamped (any M).
+// relu-mask multiply.  K % 64 == 0 (launch_gemm_nt checks it), rows clamped (any M).
 enum { EPI_NONE = 0, EPI_RELU = 1, EPI_RESID = 2, EPI_MASK = 3 };
 
-template <int EPI>
-__global__ __launch_bounds__(256) void gemm_f32_nt_kernel(const float* __restrict__ A, const float* __restrict__ W,
-                                                          const float* __restrict__ bias, const float* __restrict__ R,
-                                                          float* __restrict__ C, int M, int N, int K) {
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int l15 = lane & 15, q = lane >> 4;
-  const int m0 = blockIdx.y * 64 + (wid >> 1) * 32;
-  const int n0 = blockIdx.x * 64 + (wid & 1) * 32;
-  const float* ap[2];
-  const float* wp[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    int r = m0 + 16 * i + l15;
-    r = r < M ? r : M - 1;
-    ap[i] = A + (size_t)r * K + 4 * q;
-    wp[i] = W + (size_t)(n0 + 16 * i + l15) * K + 4 * q;
-  }
-  f32x4 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-  // software pipeline, prefetch distance 2 K-steps (the problem is L2 resident but only ~2 waves share a SIMD, so
-  // an un-prefetched loop exposes the whole L2 latency every 16 MFMAs: measured 34 % of the fp32 MFMA peak)
-  // Loads past the end re-read the last K-step (clamped address, result unused): keeping the loads unconditional lets
-  // the compiler emit counted vmcnt waits - with branches around them it falls back to vmcnt(0) and the prefetch is lost.
-  f32x4 a0[2], b0[2], a1[2], b1[2], a2[2], b2[2];
-  const int klast = K - 16;
-  auto ld = [&](f32x4 (&a)[2], f32x4 (&b)[2], int k0) {
-    k0 = k0 < klast ? k0 : klast;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      a[i] = *reinterpret_cast<const f32x4*>(ap[i] + k0);
-      b[i] = *reinterpret_cast<const f32x4*>(wp[i] + k0);
-    }
-  };
-  auto mm = [&](const f32x4 (&a)[2], const f32x4 (&b)[2]) {
-#pragma unroll
-    for (int s = 0; s < 4; ++s)
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i][s], b[j][s], acc[i][j], 0, 0, 0);
-  };
-  ld(a0, b0, 0);
-  ld(a1, b1, 16);
-  const int nsteps = K >> 4;
-  int st = 0;
-  for (; st + 3 <= nsteps; st += 3) {   // three register sets rotate; prefetch distance 2 K-steps
-    ld(a2, b2, (st + 2) << 4);
-    mm(a0, b0);
-    ld(a0, b0, (st + 3) << 4);
-    mm(a1, b1);
-    ld(a1, b1, (st + 4) << 4);
-    mm(a2, b2);
-  }
-  if (st < nsteps) mm(a0, b0);
-  if (st + 1 < nsteps) mm(a1, b1);
-  // D layout: col = lane&15, row = (lane>>4)*4 + reg
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int col = n0 + 16 * j + l15;
-      const float bv = bias ? bias[col] : 0.f;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = m0 + 16 * i + q * 4 + r;
-        if (row < M) {
-          float v = acc[i][j][r] + bv;
-          const size_t o = (size_t)row * N + col;
-          if (EPI == EPI_RELU) v = fmaxf(v, 0.f);
-          if (EPI == EPI_RESID) v += R[o];
-          if (EPI == EPI_MASK) v = R[o] > 0.f ? v : 0.f;
-          C[o] = v;
-        }
-      }
-    }
-}
-
-// LDS-staged version of the same GEMM (used when K % 32 == 0): the fragment-shaped global loads of the kernel above
-// (16 rows x 64 B per wave instruction) are address-processing bound; here each 32-float-deep operand slab is brought
-// in as full 128-byte rows by LDS-DMA (XOR-swizzled like the bf16 GEMM tiles) and fragments come from ds_read_b128.
+// LDS-staged: fragment-shaped global loads (16 rows x 64 B per wave instruction) are address-processing bound; here each
+// 32-float-deep operand slab is brought in as full 128-byte rows by LDS-DMA (XOR-swizzled like the bf16 GEMM tiles) and
+// fragments come from ds_read_b128.
 // One workgroup = 64 x (32*WN) outputs, NWM x 2 waves of (64/NWM) x (16*WN); 3-deep ring with counted vmcnt waits.
 // WN = 3 (64x96 tiles) is used when N % 96 == 0: for D = 768 that makes BT=2048 x 768 exactly 256 workgroups (one
 // per CU) and x 2304 exactly 3 per CU, instead of 1.5 / 4.5 with 64x64 tiles, and gives 48 MFMAs per barrier.
@@ -169,7 +109,7 @@ constexpr int nt_lds_bytes() { return NT_NST * SPB * (BM / 8 + 4 * WN) * 1024; }
 // SPB = 2: TWO 32-deep slabs per ring stage and barrier (K / 32 even).  A K-step of a small tile is ~650 cycles of wait + barrier + DMA
 // issue + fragment-read latency around 256 cycles of dependent MFMAs (cycle-counter probe, round 4): pairing the slabs halves the
 // number of such steps, and the ring (NT_NST stages of two slabs) holds twice as many slabs in flight.  Same contraction order.
-template <int EPI, int WN, int NWM, int NT_NST, int SPLIT, int MI = 4 / NWM, int HALVES = 1, int SPB = 1>
+template <int EPI, int WN, int NWM, int NT_NST, Prec P, int MI = 4 / NWM, int HALVES = 1, int SPB = 1>
 __device__ __forceinline__ void gemm_f32_nt_lds_body(char* lds, const float* __restrict__ A, const float* __restrict__ W,
                                                      const float* __restrict__ bias, const float* __restrict__ R,
                                                      float* __restrict__ C, int M, int N, int K, int bx, int by) {
@@ -216,18 +156,11 @@ __device__ __forceinline__ void gemm_f32_nt_lds_body(char* lds, const float* __r
   // wait until slab kt has landed: the (NT_NST - 2) newer slabs of this wave (PW pieces each) may stay in flight
   auto wait_ahead = [&](int ahead) {
     const int cnt = ahead * SPB * (hi ? PW_HI : PW_LO);
-    switch (cnt) {   // s_waitcnt needs an immediate
+    switch (cnt) {   // s_waitcnt needs an immediate: the counts of the forms launch_gemm_nt and the dgrad_wgrad kernels run
       case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
       case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
       case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
       case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-      case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-      case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-      case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-      case 9: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
-      case 10: asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); break;
-      case 12: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
-      case 15: asm volatile("s_waitcnt vmcnt(15)" ::: "memory"); break;
       default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;   // (conservative)
     }
   };
@@ -272,50 +205,26 @@ __device__ __forceinline__ void gemm_f32_nt_lds_body(char* lds, const float* __r
 #pragma unroll
     for (int sub = 0; sub < SPB; ++sub) {
     const char* cur = lds + (ring_now * SPB + sub) * SLAB;
-    if (SPLIT == 2) {
-      // bf16 operands / fp32 accumulate (TSPO_SEL_BF16): the slab's fp32 values rounded to bf16 in registers, ONE MFMA per tile and slab
+    if constexpr (P != PREC_F32) {
+      // one bf16 MFMA step spans the whole 32-deep slab: lane (row l15, q) owns k = 8q..8q+7 = 16-byte chunks 2q, 2q+1
       const int c0 = (((2 * q) ^ sw) << 4), c1 = (((2 * q + 1) ^ sw) << 4);
-      bf16x8 ah[MI], bh[WN];
+      BfOp<P> a[MI], b[WN];
 #pragma unroll
       for (int i = 0; i < MI; ++i) {
         const f32x4 u = *reinterpret_cast<const f32x4*>(cur + offA[i] + c0), v = *reinterpret_cast<const f32x4*>(cur + offA[i] + c1);
         const float x[8] = {u[0], u[1], u[2], u[3], v[0], v[1], v[2], v[3]};
-        ah[i] = round_bf16x8(x);
+        bf_pack8(a[i], x);
       }
 #pragma unroll
       for (int j = 0; j < WN; ++j) {
         const f32x4 u = *reinterpret_cast<const f32x4*>(cur + offW[j] + c0), v = *reinterpret_cast<const f32x4*>(cur + offW[j] + c1);
         const float x[8] = {u[0], u[1], u[2], u[3], v[0], v[1], v[2], v[3]};
-        bh[j] = round_bf16x8(x);
+        bf_pack8(b[j], x);
       }
 #pragma unroll
       for (int i = 0; i < MI; ++i)
 #pragma unroll
-        for (int j = 0; j < WN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-    } else if (SPLIT) {
-      // one bf16 MFMA spans the whole 32-deep slab: lane (row l15, q) owns k = 8q..8q+7 = 16-byte chunks 2q, 2q+1
-      const int c0 = (((2 * q) ^ sw) << 4), c1 = (((2 * q + 1) ^ sw) << 4);
-      bf16x8 ah[MI], al[MI], bh[WN], bl[WN];
-#pragma unroll
-      for (int i = 0; i < MI; ++i) {
-        const f32x4 u = *reinterpret_cast<const f32x4*>(cur + offA[i] + c0), v = *reinterpret_cast<const f32x4*>(cur + offA[i] + c1);
-        const float x[8] = {u[0], u[1], u[2], u[3], v[0], v[1], v[2], v[3]};
-        split_bf16x8(x, ah[i], al[i]);
-      }
-#pragma unroll
-      for (int j = 0; j < WN; ++j) {
-        const f32x4 u = *reinterpret_cast<const f32x4*>(cur + offW[j] + c0), v = *reinterpret_cast<const f32x4*>(cur + offW[j] + c1);
-        const float x[8] = {u[0], u[1], u[2], u[3], v[0], v[1], v[2], v[3]};
-        split_bf16x8(x, bh[j], bl[j]);
-      }
-#pragma unroll
-      for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < WN; ++j) {
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-        }
+        for (int j = 0; j < WN; ++j) acc[i][j] = bf_mfma(a[i], b[j], acc[i][j]);
     } else {
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
@@ -355,16 +264,16 @@ __device__ __forceinline__ void gemm_f32_nt_lds_body(char* lds, const float* __r
     }
 }
 
-template <int EPI, int WN, int NWM, int NT_NST, int SPLIT, int MI = 4 / NWM, int SPB = 1>
+template <int EPI, int WN, int NWM, int NT_NST, Prec P, int MI = 4 / NWM, int SPB = 1>
 __global__ __launch_bounds__(NWM * 128) void gemm_f32_nt_lds_kernel(const float* __restrict__ A, const float* __restrict__ W,
                                                                     const float* __restrict__ bias,
                                                                     const float* __restrict__ R, float* __restrict__ C,
                                                                     int M, int N, int K) {
   __shared__ __attribute__((aligned(16))) char lds[nt_lds_bytes<WN, NT_NST, 16 * NWM * MI, SPB>()];   // the only LDS object
-  gemm_f32_nt_lds_body<EPI, WN, NWM, NT_NST, SPLIT, MI, 1, SPB>(lds, A, W, bias, R, C, M, N, K, blockIdx.x, blockIdx.y);
+  gemm_f32_nt_lds_body<EPI, WN, NWM, NT_NST, P, MI, 1, SPB>(lds, A, W, bias, R, C, M, N, K, blockIdx.x, blockIdx.y);
 }
 
-template <int EPI, int SPLIT>
+template <int EPI, Prec P>
 int launch_gemm_nt_p(const float* A, const float* W, const float* bias, const float* R, float* C, int M, int N, int K,
                      hipStream_t st) {
   const int mt = (M + 63) / 64;
@@ -375,45 +284,45 @@ int launch_gemm_nt_p(const float* A, const float* W, const float* bias, const fl
   // contraction order per output element as the large form: bitwise the same results.  At BT = 2048 the DxD forwards take 28 us with
   // ANY of the tilings (64x96, 32x96, 32x64, 32x32: +-0.3 % on the step), and a 64-row problem still takes 9.3-10 us: the floor is the
   // serial chain of 24 K-steps (barrier, DMA issue, fragment reads, 8 dependent MFMAs: ~800 cycles each), not the tile shape.
-  if (K % 32 == 0 && N % 32 == 0 && (long)(N / 96) * mt < 256) {
-    if (K % 64 == 0)   // two slabs per barrier: a 512-row DxD launch 27.1 k -> 23.2 k cycles, a 64-row one 21.4 k -> 16.9 k (probe)
-      hipLaunchKernelGGL((gemm_f32_nt_lds_kernel<EPI, 1, 2, 3, SPLIT, 1, 2>), dim3(N / 32, (M + 31) / 32), dim3(256), 0, st, A, W, bias, R,
-                         C, M, N, K);
-    else
-      hipLaunchKernelGGL((gemm_f32_nt_lds_kernel<EPI, 1, 2, 3, SPLIT, 1>), dim3(N / 32, (M + 31) / 32), dim3(256), 0, st, A, W, bias, R,
-                         C, M, N, K);
+  if (N % 32 == 0 && (long)(N / 96) * mt < 256) {
+    // two slabs per barrier: a 512-row DxD launch 27.1 k -> 23.2 k cycles, a 64-row one 21.4 k -> 16.9 k (probe)
+    hipLaunchKernelGGL((gemm_f32_nt_lds_kernel<EPI, 1, 2, 3, P, 1, 2>), dim3(N / 32, (M + 31) / 32), dim3(256), 0, st, A, W, bias, R, C,
+                       M, N, K);
     return tspo::check_launch("selector gemm_nt");
   }
-  if (K % 64 == 0 && N % 96 == 0 && (long)(N / 96) * mt <= 256) {
+  if (N % 96 == 0 && (long)(N / 96) * mt <= 256) {
     // one workgroup per CU (DxD at BT = 2048): two slabs per barrier, two such stages (80 KB): 64.2 k -> 55.6 k cycles per launch
     // (probe; with three stages 59.3 k); the epilogue's share 8.0 k -> 4.4 k by fetching its operands before the K-loop
-    hipLaunchKernelGGL((gemm_f32_nt_lds_kernel<EPI, 3, 4, 2, SPLIT, 1, 2>), dim3(N / 96, mt), dim3(512), 0, st, A, W, bias, R, C, M, N, K);
+    hipLaunchKernelGGL((gemm_f32_nt_lds_kernel<EPI, 3, 4, 2, P, 1, 2>), dim3(N / 96, mt), dim3(512), 0, st, A, W, bias, R, C, M, N, K);
     return tspo::check_launch("selector gemm_nt");
   }
   // between one and two 64x96 workgroups per CU (Dx3D at BT = 1024: 384) the CUs that hold two set the time: 32x96 tiles (four waves,
   // 48 KB rings) make it 768 = three per CU - 46 -> 40 us, same box; same contraction order per output element
-  if (K % 32 == 0 && N % 96 == 0 && (long)(N / 96) * mt > 256 && (long)(N / 96) * mt < 512) {
-    hipLaunchKernelGGL((gemm_f32_nt_lds_kernel<EPI, 3, 2, 3, SPLIT, 1>), dim3(N / 96, (M + 31) / 32), dim3(256), 0, st, A, W, bias, R, C, M, N, K);
+  if (N % 96 == 0 && (long)(N / 96) * mt > 256 && (long)(N / 96) * mt < 512) {
+    hipLaunchKernelGGL((gemm_f32_nt_lds_kernel<EPI, 3, 2, 3, P, 1>), dim3(N / 96, (M + 31) / 32), dim3(256), 0, st, A, W, bias, R, C, M, N, K);
     return tspo::check_launch("selector gemm_nt");
   }
   // ring depth 3 keeps two workgroups (16 waves) per CU; when the grid holds more than two workgroups per CU a 2-deep
   // ring (40 KB) lets three run at once instead of leaving the third for a half-empty second round
-  if (K % 32 == 0 && N % 96 == 0) {
+  if (N % 96 == 0) {
     if ((long)(N / 96) * mt > 512)
-      hipLaunchKernelGGL((gemm_f32_nt_lds_kernel<EPI, 3, 4, 2, SPLIT>), dim3(N / 96, mt), dim3(512), 0, st, A, W, bias, R, C, M, N, K);
+      hipLaunchKernelGGL((gemm_f32_nt_lds_kernel<EPI, 3, 4, 2, P>), dim3(N / 96, mt), dim3(512), 0, st, A, W, bias, R, C, M, N, K);
     else   // (a 6-deep ring for the split-precision case measured slower: 24-26 us vs 21-23 us for the DxD GEMMs)
-      hipLaunchKernelGGL((gemm_f32_nt_lds_kernel<EPI, 3, 4, 3, SPLIT>), dim3(N / 96, mt), dim3(512), 0, st, A, W, bias, R, C, M, N, K);
-  } else if (K % 32 == 0)
-    hipLaunchKernelGGL((gemm_f32_nt_lds_kernel<EPI, 2, 4, 3, SPLIT>), dim3(N / 64, mt), dim3(512), 0, st, A, W, bias, R, C, M, N, K);
-  else
-    hipLaunchKernelGGL((gemm_f32_nt_kernel<EPI>), dim3(N / 64, mt), dim3(256), 0, st, A, W, bias, R, C, M, N, K);   // (always exact)
+      hipLaunchKernelGGL((gemm_f32_nt_lds_kernel<EPI, 3, 4, 3, P>), dim3(N / 96, mt), dim3(512), 0, st, A, W, bias, R, C, M, N, K);
+  } else
+    hipLaunchKernelGGL((gemm_f32_nt_lds_kernel<EPI, 2, 4, 3, P>), dim3(N / 64, mt), dim3(512), 0, st, A, W, bias, R, C, M, N, K);
   return tspo::check_launch("selector gemm_nt");
 }
 template <int EPI>
 int launch_gemm_nt(const float* A, const float* W, const float* bias, const float* R, float* C, int M, int N, int K,
-                   hipStream_t st, int split = 0) {   // 0 exact fp32, 1 bf16x3 (hi/lo split), 2 bf16 operands
-  if (split == 2 && K % 32 == 0) return launch_gemm_nt_p<EPI, 2>(A, W, bias, R, C, M, N, K, st);
-  return split == 1 ? launch_gemm_nt_p<EPI, 1>(A, W, bias, R, C, M, N, K, st) : launch_gemm_nt_p<EPI, 0>(A, W, bias, R, C, M, N, K, st);
+                   hipStream_t st, Prec p) {
+  // every form stages 32-deep slabs and the small-M / one-per-CU forms pair them; N % 32 == 0 always (N = D or 3D, D % 64 == 0)
+  TSPO_REQUIRE(K % 64 == 0, "selector gemm_nt: K=%d must be a multiple of 64", K);
+  switch (p) {
+    case PREC_BF16X3: return launch_gemm_nt_p<EPI, PREC_BF16X3>(A, W, bias, R, C, M, N, K, st);
+    case PREC_BF16: return launch_gemm_nt_p<EPI, PREC_BF16>(A, W, bias, R, C, M, N, K, st);
+    default: return launch_gemm_nt_p<EPI, PREC_F32>(A, W, bias, R, C, M, N, K, st);
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -1144,10 +1053,12 @@ __global__ __launch_bounds__(256) void score_bwd_kernel(const float* __restrict_
 // weight-gradient GEMM: Cp[s][i][j] = sum_{m in chunk s} dY[m][i] * X[m][j]
 // ("TN": the contraction runs over rows).  One wave = 64x64 outputs made of 16
 // MFMA tiles with an interleaved feature map (tile c holds features 4*l+c) so
-// that every operand load and every store is a contiguous float4.
+// that every operand load and every store is a contiguous float4.  Direct loads: the fallback for NI or NJ not a multiple of
+// 128 (PREC_F32 or PREC_BF16; weight_grad maps PREC_BF16X3 to PREC_F32 here).  Rows past the chunk end are clamped and their
+// contribution zeroed by a multiplier (no branch around the loads, so the compiler keeps counted vmcnt waits).
+template <Prec P>
 __global__ __launch_bounds__(256) void gemm_f32_tn_kernel(const float* __restrict__ dY, const float* __restrict__ X,
-                                                          float* __restrict__ Cp, int Mrows, int NI, int NJ,
-                                                          int chunk) {
+                                                          float* __restrict__ Cp, int Mrows, int NI, int NJ, int chunk) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int l15 = lane & 15, q = lane >> 4;
   const int i0 = blockIdx.y * 128 + (wid >> 1) * 64;
@@ -1162,38 +1073,65 @@ __global__ __launch_bounds__(256) void gemm_f32_tn_kernel(const float* __restric
     for (int b = 0; b < 4; ++b) acc[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
   const float* yp = dY + i0 + 4 * l15;
   const float* xp = X + j0 + 4 * l15;
-  // rows past the chunk end are clamped and their contribution zeroed by a multiplier (no branch around the loads,
-  // so the compiler keeps counted vmcnt waits and the prefetch distance of 2 survives)
   const int rlast = me > mb ? me - 1 : mb;
-  auto ld = [&](f32x4& a, f32x4& b, int m) {
-    const int r = m + q;
-    const int rc = r < rlast ? r : rlast;
-    const float keep = (r < me) ? 1.f : 0.f;
-    a = *reinterpret_cast<const f32x4*>(yp + (size_t)rc * NI) * keep;
-    b = *reinterpret_cast<const f32x4*>(xp + (size_t)rc * NJ);
-  };
-  auto mm = [&](const f32x4& a, const f32x4& b) {
+  if constexpr (P == PREC_F32) {
+    // 4 rows per k-step, prefetch distance 2 k-steps
+    auto ld = [&](f32x4& a, f32x4& b, int m) {
+      const int r = m + q;
+      const int rc = r < rlast ? r : rlast;
+      const float keep = (r < me) ? 1.f : 0.f;
+      a = *reinterpret_cast<const f32x4*>(yp + (size_t)rc * NI) * keep;
+      b = *reinterpret_cast<const f32x4*>(xp + (size_t)rc * NJ);
+    };
+    auto mm = [&](const f32x4& a, const f32x4& b) {
 #pragma unroll
-    for (int ca = 0; ca < 4; ++ca)
+      for (int ca = 0; ca < 4; ++ca)
 #pragma unroll
-      for (int cb = 0; cb < 4; ++cb) acc[ca][cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[ca], b[cb], acc[ca][cb], 0, 0, 0);
-  };
-  f32x4 a0, b0, a1, b1, a2, b2;
-  if (me > mb) {
-    ld(a0, b0, mb);
-    ld(a1, b1, mb + 4);
-    const int nsteps = (me - mb + 3) >> 2;
-    int st = 0;
-    for (; st + 3 <= nsteps; st += 3) {
-      ld(a2, b2, mb + ((st + 2) << 2));
-      mm(a0, b0);
-      ld(a0, b0, mb + ((st + 3) << 2));
-      mm(a1, b1);
-      ld(a1, b1, mb + ((st + 4) << 2));
-      mm(a2, b2);
+        for (int cb = 0; cb < 4; ++cb) acc[ca][cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[ca], b[cb], acc[ca][cb], 0, 0, 0);
+    };
+    f32x4 a0, b0, a1, b1, a2, b2;
+    if (me > mb) {
+      ld(a0, b0, mb);
+      ld(a1, b1, mb + 4);
+      const int nsteps = (me - mb + 3) >> 2;
+      int st = 0;
+      for (; st + 3 <= nsteps; st += 3) {
+        ld(a2, b2, mb + ((st + 2) << 2));
+        mm(a0, b0);
+        ld(a0, b0, mb + ((st + 3) << 2));
+        mm(a1, b1);
+        ld(a1, b1, mb + ((st + 4) << 2));
+        mm(a2, b2);
+      }
+      if (st < nsteps) mm(a0, b0);
+      if (st + 1 < nsteps) mm(a1, b1);
     }
-    if (st < nsteps) mm(a0, b0);
-    if (st + 1 < nsteps) mm(a1, b1);
+  } else {
+    // 32 rows per k-step: lane (l15, q) reads rows 8q..8q+7 (8 float4 per operand, 4 feature tiles each)
+    for (int m0 = mb; m0 < me; m0 += 32) {
+      f32x4 a4[8], b4[8];
+#pragma unroll
+      for (int r = 0; r < 8; ++r) {
+        const int m = m0 + 8 * q + r;
+        const int rc = m < rlast ? m : rlast;
+        a4[r] = *reinterpret_cast<const f32x4*>(yp + (size_t)rc * NI) * ((m < me) ? 1.f : 0.f);
+        b4[r] = *reinterpret_cast<const f32x4*>(xp + (size_t)rc * NJ);
+      }
+      BfOp<P> bh[4];
+#pragma unroll
+      for (int cb = 0; cb < 4; ++cb) {
+        const float x[8] = {b4[0][cb], b4[1][cb], b4[2][cb], b4[3][cb], b4[4][cb], b4[5][cb], b4[6][cb], b4[7][cb]};
+        bf_pack8(bh[cb], x);
+      }
+#pragma unroll
+      for (int ca = 0; ca < 4; ++ca) {
+        const float x[8] = {a4[0][ca], a4[1][ca], a4[2][ca], a4[3][ca], a4[4][ca], a4[5][ca], a4[6][ca], a4[7][ca]};
+        BfOp<P> ah;
+        bf_pack8(ah, x);
+#pragma unroll
+        for (int cb = 0; cb < 4; ++cb) acc[ca][cb] = bf_mfma(ah, bh[cb], acc[ca][cb]);
+      }
+    }
   }
   float* cp = Cp + (size_t)s * NI * NJ;
 #pragma unroll
@@ -1201,60 +1139,6 @@ __global__ __launch_bounds__(256) void gemm_f32_tn_kernel(const float* __restric
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int i = i0 + 4 * (q * 4 + r) + ca;  // D row (q*4+r) of tile ca -> feature 4*row + ca
-      f32x4 v = {acc[ca][0][r], acc[ca][1][r], acc[ca][2][r], acc[ca][3][r]};
-      *reinterpret_cast<f32x4*>(cp + (size_t)i * NJ + j0 + 4 * l15) = v;
-    }
-}
-
-// bf16-operand form of the kernel above (TSPO_SEL_BF16_MIXED; the fallback for NI or NJ not a multiple of 128): same 64x64 wave tile
-// and interleaved feature map, 32 contraction rows per k-step - lane (l15, q) reads rows 8q..8q+7 (8 float4 per operand, 4 feature
-// tiles each), rounds them to bf16 in registers and issues one v_mfma_f32_16x16x32_bf16 per tile pair.
-__global__ __launch_bounds__(256) void gemm_f32_tn_bf16_kernel(const float* __restrict__ dY, const float* __restrict__ X,
-                                                               float* __restrict__ Cp, int Mrows, int NI, int NJ, int chunk) {
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int l15 = lane & 15, q = lane >> 4;
-  const int i0 = blockIdx.y * 128 + (wid >> 1) * 64;
-  const int j0 = blockIdx.x * 128 + (wid & 1) * 64;
-  if (i0 >= NI || j0 >= NJ) return;
-  const int s = blockIdx.z;
-  const int mb = s * chunk, me = min(Mrows, mb + chunk);
-  f32x4 acc[4][4];
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 4; ++b) acc[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  const float* yp = dY + i0 + 4 * l15;
-  const float* xp = X + j0 + 4 * l15;
-  const int rlast = me > mb ? me - 1 : mb;
-  for (int m0 = mb; m0 < me; m0 += 32) {
-    f32x4 a4[8], b4[8];
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {   // rows past the chunk end: clamped address, contribution zeroed
-      const int m = m0 + 8 * q + r;
-      const int rc = m < rlast ? m : rlast;
-      a4[r] = *reinterpret_cast<const f32x4*>(yp + (size_t)rc * NI) * ((m < me) ? 1.f : 0.f);
-      b4[r] = *reinterpret_cast<const f32x4*>(xp + (size_t)rc * NJ);
-    }
-    bf16x8 bh[4];
-#pragma unroll
-    for (int cb = 0; cb < 4; ++cb) {
-      const float x[8] = {b4[0][cb], b4[1][cb], b4[2][cb], b4[3][cb], b4[4][cb], b4[5][cb], b4[6][cb], b4[7][cb]};
-      bh[cb] = round_bf16x8(x);
-    }
-#pragma unroll
-    for (int ca = 0; ca < 4; ++ca) {
-      const float x[8] = {a4[0][ca], a4[1][ca], a4[2][ca], a4[3][ca], a4[4][ca], a4[5][ca], a4[6][ca], a4[7][ca]};
-      const bf16x8 ah = round_bf16x8(x);
-#pragma unroll
-      for (int cb = 0; cb < 4; ++cb) acc[ca][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh[cb], acc[ca][cb], 0, 0, 0);
-    }
-  }
-  float* cp = Cp + (size_t)s * NI * NJ;
-#pragma unroll
-  for (int ca = 0; ca < 4; ++ca)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int i = i0 + 4 * (q * 4 + r) + ca;
       f32x4 v = {acc[ca][0][r], acc[ca][1][r], acc[ca][2][r], acc[ca][3][r]};
       *reinterpret_cast<f32x4*>(cp + (size_t)i * NJ + j0 + 4 * l15) = v;
     }
@@ -1270,14 +1154,14 @@ __global__ __launch_bounds__(256) void gemm_f32_tn_bf16_kernel(const float* __re
 // workgroups have 512 threads).  Same contraction order per output element either way.  `cpart` (optional): the
 // workgroups of feature-tile column 0 also emit the column sums of their dY rows (= this split's bias-gradient
 // partial, cpart[s * cstride + i]) from the fragments they read anyway.
-// BF = 1 (TSPO_SEL_BF16_MIXED): bf16 operands / fp32 accumulate, slabs of 32 contraction rows = one v_mfma_f32_16x16x32_bf16 k-step:
-// lane (l15, q) owns rows 8q..8q+7 (8 fragment reads per operand, rounded to bf16 in registers) - one MFMA per tile pair and slab where
-// the exact form issues eight.  The bias column sums (`cpart`) are taken from the fp32 values before the rounding.
-template <int NW, int NST, int BF = 0>
+// P != PREC_F32: slabs of 32 contraction rows = one v_mfma_f32_16x16x32_bf16 k-step: lane (l15, q) owns rows 8q..8q+7 (8 fragment
+// reads per operand, packed to bf16 in registers) - one MFMA (bf16x3: three) per tile pair and slab where the exact form issues eight.
+// The bias column sums (`cpart`) are taken from the fp32 values before the packing.
+template <int NW, int NST, Prec P>
 __device__ __forceinline__ void gemm_f32_tn_lds_body(char* lds, const float* __restrict__ dY, const float* __restrict__ X,
                                                      float* __restrict__ Cp, float* __restrict__ cpart, int cstride,
                                                      int Mrows, int NI, int NJ, int chunk, int bj, int bi, int s) {
-  constexpr int ROWS = BF ? 32 : TN_ROWS;   // contraction rows per slab
+  constexpr int ROWS = P != PREC_F32 ? 32 : TN_ROWS;   // contraction rows per slab
   constexpr int HALF = ROWS * 512;          // bytes of one operand's slab (rows of 128 floats)
   constexpr int WJ = NW / 2;            // waves along j
   constexpr int CB = 4 / (WJ / 2);      // interleaved 16-column tiles per wave along j: 4 (64 columns) or 2 (32 columns)
@@ -1331,10 +1215,10 @@ __device__ __forceinline__ void gemm_f32_tn_lds_body(char* lds, const float* __r
     __builtin_amdgcn_s_barrier();   // slab t visible to all waves; everyone is done with slab t-1 -> its slot is free
     if (t + NST - 1 < nst) stage(t + NST - 1);
     const char* cur = lds + (t % NST) * 2 * HALF;
-    if (BF) {
+    if constexpr (P != PREC_F32) {
       // rows m = 8q + r (m & 1 = r & 1), packed to bf16 pairs as soon as two are read (the fp32 fragments die early: the 8-wave form
       // stays within the register budget of two workgroups per CU)
-      union { bf16x8 v; uint32_t u[4]; } ah[4], bh[CB];
+      BfOp<P> ah[4], bh[CB];
 #pragma unroll
       for (int r = 0; r < 8; r += 2) {
         f32x4 a[2];
@@ -1348,14 +1232,14 @@ __device__ __forceinline__ void gemm_f32_tn_lds_body(char* lds, const float* __r
           if (want_cs) csum += a[h];
         }
 #pragma unroll
-        for (int ca = 0; ca < 4; ++ca) ah[ca].u[r / 2] = pack_bf16x2(a[0][ca], a[1][ca]);
+        for (int ca = 0; ca < 4; ++ca) bf_pack(ah[ca], r / 2, a[0][ca], a[1][ca]);
 #pragma unroll
-        for (int cb = 0; cb < CB; ++cb) bh[cb].u[r / 2] = pack_bf16x2(b[0][cb], b[1][cb]);
+        for (int cb = 0; cb < CB; ++cb) bf_pack(bh[cb], r / 2, b[0][cb], b[1][cb]);
       }
 #pragma unroll
       for (int ca = 0; ca < 4; ++ca)
 #pragma unroll
-        for (int cb = 0; cb < CB; ++cb) acc[ca][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[ca].v, bh[cb].v, acc[ca][cb], 0, 0, 0);
+        for (int cb = 0; cb < CB; ++cb) acc[ca][cb] = bf_mfma(ah[ca], bh[cb], acc[ca][cb]);
     } else {
 #pragma unroll
     for (int ks = 0; ks < TN_ROWS / 4; ++ks) {
@@ -1403,16 +1287,16 @@ __device__ __forceinline__ void gemm_f32_tn_lds_body(char* lds, const float* __r
 // form (plane s of Cp / cpart, reduced later).
 // LDS: row m of a slab = 64 floats (256 B = all 64 banks), so the two 16-lane groups a ds_read_b64 serves per cycle (rows m, m+1)
 // would hit the same banks: the DMA stores the 128-byte halves of odd rows swapped, the reads undo it.
-// BF = 1 (TSPO_SEL_BF16_MIXED): each K-group takes 32 rows of a 64-row step (ring stages of 2 x 16 KB) as one
-// v_mfma_f32_16x16x32_bf16 k-step - lane (l15, q) owns rows 8q..8q+7, operands rounded to bf16 in registers; fp32 column sums.
-template <int NST, int KG, int BF = 0>
+// P != PREC_F32: each K-group takes 32 rows of a 64-row step (ring stages of 2 x 16 KB) as one
+// v_mfma_f32_16x16x32_bf16 k-step - lane (l15, q) owns rows 8q..8q+7, operands packed to bf16 in registers; fp32 column sums.
+template <int NST, int KG, Prec P>
 __device__ __forceinline__ void gemm_f32_tn64_body(char* lds, const float* __restrict__ dY, const float* __restrict__ X,
                                                    float* __restrict__ Cp, float* __restrict__ cpart, int cstride,
                                                    float* __restrict__ sq_partial, int accumulate, int Mrows, int NI, int NJ,
                                                    int chunk, int bj, int bi, int s, int wg_index) {
   // KG = 2: 8 waves; waves 4..7 (K-group 1) take rows 16..31 of every 32-row step and their accumulators are added to K-group 0's
   // through LDS at the end (fixed order): twice the waves per CU for the same tile count, half the dependent chain
-  constexpr int KROWS = BF ? 32 : TN_ROWS;        // contraction rows per K-group and step
+  constexpr int KROWS = P != PREC_F32 ? 32 : TN_ROWS;   // contraction rows per K-group and step
   constexpr int STEP = KROWS * KG, KSL = KROWS * 512, SLAB = KSL * KG;   // (KSL: one K-group's A | B rows of 256 B)
   constexpr int PD = KROWS / 16;                  // DMA instructions per wave and operand (4 rows each)
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
@@ -1430,7 +1314,7 @@ __device__ __forceinline__ void gemm_f32_tn64_body(char* lds, const float* __res
   const bool want_cs = cpart != nullptr && bj == 0 && wj == 0;   // wave-uniform
   const int nst = me > mb ? (me - mb + STEP - 1) / STEP : 0;
   const int rlast = me > mb ? me - 1 : mb;
-  // DMA: wave w moves rows 4w..4w+3 of the step (BF: rows 8w..8w+7), both operands (one 1 KB piece each per 4 rows); lane (r4, chunk)
+  // DMA: wave w moves rows 4w..4w+3 of the step (bf16: rows 8w..8w+7), both operands (one 1 KB piece each per 4 rows); lane (r4, chunk)
   // fetches the 16 bytes whose LDS place is row r4, chunk `chunk`, i.e. source half (chunk >> 3) ^ (r4 & 1)
   const int r4 = lane >> 4, ch = lane & 15;
   const int scol = ((((ch >> 3) ^ (r4 & 1)) << 5) + ((ch & 7) << 2));
@@ -1461,9 +1345,9 @@ __device__ __forceinline__ void gemm_f32_tn64_body(char* lds, const float* __res
     __builtin_amdgcn_s_barrier();   // step t visible to all waves; everyone is done with step t-1 -> its slot is free
     if (t + NST - 1 < nst) stage(t + NST - 1);
     const char* cur = lds + (t % NST) * SLAB;
-    if (BF) {
+    if constexpr (P != PREC_F32) {
       // rows m = 8q + r (m & 1 = r & 1), packed to bf16 pairs as soon as two are read
-      union { bf16x8 v; uint32_t u[4]; } ah[2], bh[2];
+      BfOp<P> ah[2], bh[2];
 #pragma unroll
       for (int r = 0; r < 8; r += 2) {
         f32x2 a[2], b[2];
@@ -1477,14 +1361,14 @@ __device__ __forceinline__ void gemm_f32_tn64_body(char* lds, const float* __res
         }
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
-          ah[c].u[r / 2] = pack_bf16x2(a[0][c], a[1][c]);
-          bh[c].u[r / 2] = pack_bf16x2(b[0][c], b[1][c]);
+          bf_pack(ah[c], r / 2, a[0][c], a[1][c]);
+          bf_pack(bh[c], r / 2, b[0][c], b[1][c]);
         }
       }
 #pragma unroll
       for (int ca = 0; ca < 2; ++ca)
 #pragma unroll
-        for (int cb = 0; cb < 2; ++cb) acc[ca][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[ca].v, bh[cb].v, acc[ca][cb], 0, 0, 0);
+        for (int cb = 0; cb < 2; ++cb) acc[ca][cb] = bf_mfma(ah[ca], bh[cb], acc[ca][cb]);
     } else {
 #pragma unroll
     for (int ks = 0; ks < TN_ROWS / 4; ++ks) {
@@ -1564,36 +1448,38 @@ __device__ __forceinline__ void gemm_f32_tn64_body(char* lds, const float* __res
   }
 }
 
-// (BF: a 2-deep ring of 64-row steps, 64 KB - the same rows in flight as the exact form's 3-deep ring of 32-row steps)
-template <int BF>
+// (bf16: a 2-deep ring of 64-row steps, 64 KB - the same rows in flight as the exact form's 3-deep ring of 32-row steps)
+template <Prec P>
 __global__ __launch_bounds__(512) void gemm_f32_tn64_kernel(const float* __restrict__ dY, const float* __restrict__ X,
                                                             float* __restrict__ Cp, float* __restrict__ cpart, int cstride,
                                                             float* __restrict__ sq_partial, int accumulate, int Mrows, int NI,
                                                             int NJ, int chunk) {
-  __shared__ __attribute__((aligned(16))) char lds[BF ? 2 * 32768 : 3 * 16384];
+  __shared__ __attribute__((aligned(16))) char lds[P != PREC_F32 ? 2 * 32768 : 3 * 16384];
   const int wg = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-  gemm_f32_tn64_body<BF ? 2 : 3, 2, BF>(lds, dY, X, Cp, cpart, cstride, sq_partial, accumulate, Mrows, NI, NJ, chunk, blockIdx.x,
-                                         blockIdx.y, blockIdx.z, wg);
+  gemm_f32_tn64_body<P != PREC_F32 ? 2 : 3, 2, P>(lds, dY, X, Cp, cpart, cstride, sq_partial, accumulate, Mrows, NI, NJ, chunk,
+                                                  blockIdx.x, blockIdx.y, blockIdx.z, wg);
 }
 
-// (3-deep ring here: 48 KB and <= 168 registers let three workgroups share a CU, so the 108 x S tiles of the q/k/v weight
+// (PREC_F32: 3-deep ring here: 48 KB and <= 168 registers let three workgroups share a CU, so the 108 x S tiles of the q/k/v weight
 // gradient - 756 for BT = 2048 - are resident at once instead of leaving a half-empty second round)
-// BF: 32-row slabs (32 KB per stage) in a 2-deep ring, two workgroups per CU
-template <int BF>
-__global__ __launch_bounds__(256, BF ? 2 : 3) void gemm_f32_tn_lds_kernel(const float* __restrict__ dY, const float* __restrict__ X,
-                                                                         float* __restrict__ Cp, float* __restrict__ cpart,
-                                                                         int cstride, int Mrows, int NI, int NJ, int chunk) {
-  __shared__ __attribute__((aligned(16))) char lds[BF ? 2 * 32768 : 3 * 16384];   // per stage: A 16x512 B | B 16x512 B (BF: 32 rows)
-  gemm_f32_tn_lds_body<4, BF ? 2 : 3, BF>(lds, dY, X, Cp, cpart, cstride, Mrows, NI, NJ, chunk, blockIdx.x, blockIdx.y, blockIdx.z);
+// PREC_BF16: 32-row slabs (32 KB per stage) in a 2-deep ring, two workgroups per CU
+template <Prec P>
+__global__ __launch_bounds__(256, P == PREC_BF16 ? 2 : 3) void gemm_f32_tn_lds_kernel(const float* __restrict__ dY, const float* __restrict__ X,
+                                                                                    float* __restrict__ Cp, float* __restrict__ cpart,
+                                                                                    int cstride, int Mrows, int NI, int NJ, int chunk) {
+  static_assert(P != PREC_BF16X3, "bf16x3: gemm_f32_tn_split_kernel");
+  __shared__ __attribute__((aligned(16))) char lds[P == PREC_BF16 ? 2 * 32768 : 3 * 16384];   // per stage: A | B, 16 rows (bf16: 32) x 512 B
+  gemm_f32_tn_lds_body<4, P == PREC_BF16 ? 2 : 3, P>(lds, dY, X, Cp, cpart, cstride, Mrows, NI, NJ, chunk, blockIdx.x, blockIdx.y,
+                                                     blockIdx.z);
 }
 
 // One launch = the data-gradient GEMM of a linear layer (dX = dY W: the 64x96-tile kernel above, 512-thread workgroups)
 // AND the weight-gradient tiles of the layer after it (the two are independent).  Each alone fills the 256 CUs with one
 // workgroup per CU and leaves the matrix pipes idle across its barriers; the hardware dispatches the data-gradient
 // workgroups first and the weight-gradient ones into the second slot of every CU.
-// BF (TSPO_SEL_BF16_MIXED): both halves take bf16 operands - the data gradient as the SPLIT = 2 form of the NT body, the weight-gradient
-// tiles as 32-row slabs in a 2-deep ring (the same 64 KB as the exact form's 4-deep ring of 16-row slabs).
-template <int EPI, int BF = 0>
+// PREC_F32 or PREC_BF16 (TSPO_SEL_BF16_MIXED: both halves take bf16 operands, the weight-gradient tiles as 32-row slabs in a 2-deep
+// ring - the same 64 KB as the exact form's 4-deep ring of 16-row slabs).
+template <int EPI, Prec P>
 __global__ __launch_bounds__(512, 2) void dgrad_wgrad_kernel(const float* __restrict__ A, const float* __restrict__ W,
                                                             const float* __restrict__ R, float* __restrict__ C, int M,
                                                             int N, int K, int n_nt,
@@ -1605,17 +1491,17 @@ __global__ __launch_bounds__(512, 2) void dgrad_wgrad_kernel(const float* __rest
   const int b = blockIdx.x;
   if (b < n_nt) {
     const int nx = N / 96;
-    gemm_f32_nt_lds_body<EPI, 3, 4, 3, BF ? 2 : 0>(lds, A, W, nullptr, R, C, M, N, K, b % nx, b / nx);
+    gemm_f32_nt_lds_body<EPI, 3, 4, 3, P>(lds, A, W, nullptr, R, C, M, N, K, b % nx, b / nx);
   } else {
     const int t = b - n_nt, tj = NJ >> 7, ti = NI >> 7;
-    gemm_f32_tn_lds_body<8, BF ? 2 : TN_NST, BF>(lds, dY, X, Cp, cpart, cstride, M, NI, NJ, chunk, t % tj, (t / tj) % ti,
-                                                t / (tj * ti));
+    gemm_f32_tn_lds_body<8, P != PREC_F32 ? 2 : TN_NST, P>(lds, dY, X, Cp, cpart, cstride, M, NI, NJ, chunk, t % tj, (t / tj) % ti,
+                                                          t / (tj * ti));
   }
 }
 
 // Small-M form of the launch above (BT = 512: the 64x96 data-gradient tiling has 64 workgroups): 256-thread workgroups, the data
 // gradient in 32x32 tiles (gemm_f32_nt_lds_body<.., WN 1, NWM 2, ring 3, MI 1>), the weight-gradient tiles as four waves of 64x64.
-template <int EPI, int BF = 0>
+template <int EPI, Prec P>
 __global__ __launch_bounds__(512) void dgrad_wgrad_small_kernel(const float* __restrict__ A, const float* __restrict__ W,
                                                                const float* __restrict__ R, float* __restrict__ C, int M,
                                                                int N, int K, int n_nt, int n_tiles,
@@ -1630,23 +1516,23 @@ __global__ __launch_bounds__(512) void dgrad_wgrad_small_kernel(const float* __r
   if (b < n_nt) {   // two 32x32 data-gradient tiles per workgroup (the last one may repeat a tile: same values written twice)
     const int half = threadIdx.x >> 8, nx = N / 32;
     const int tile = min(2 * b + half, n_tiles - 1);
-    gemm_f32_nt_lds_body<EPI, 1, 2, 3, BF ? 2 : 0, 1, 2>(lds + half * nt_lds_bytes<1, 3, 32>(), A, W, nullptr, R, C, M, N, K,
-                                                         tile % nx, tile / nx);
+    gemm_f32_nt_lds_body<EPI, 1, 2, 3, P, 1, 2>(lds + half * nt_lds_bytes<1, 3, 32>(), A, W, nullptr, R, C, M, N, K, tile % nx,
+                                                tile / nx);
   } else if (t64) {   // 64x64 tiles, whole contraction per workgroup (or `chunk` rows of it): see gemm_f32_tn64_body
     const int t = b - n_nt, tj = NJ >> 6, ti = NI >> 6;
-    gemm_f32_tn64_body<BF ? 2 : 3, 2, BF>(lds, dY, X, Cp, cpart, cstride, sq_partial, accumulate, M, NI, NJ, chunk, t % tj,
-                                           (t / tj) % ti, t / (tj * ti), t);
+    gemm_f32_tn64_body<P != PREC_F32 ? 2 : 3, 2, P>(lds, dY, X, Cp, cpart, cstride, sq_partial, accumulate, M, NI, NJ, chunk, t % tj,
+                                                    (t / tj) % ti, t / (tj * ti), t);
   } else {
     const int t = b - n_nt, tj = NJ >> 7, ti = NI >> 7;
-    gemm_f32_tn_lds_body<8, BF ? 2 : TN_NST, BF>(lds, dY, X, Cp, cpart, cstride, M, NI, NJ, chunk, t % tj, (t / tj) % ti,
-                                                t / (tj * ti));
+    gemm_f32_tn_lds_body<8, P != PREC_F32 ? 2 : TN_NST, P>(lds, dY, X, Cp, cpart, cstride, M, NI, NJ, chunk, t % tj, (t / tj) % ti,
+                                                          t / (tj * ti));
   }
 }
 
-// Split-precision (bf16x3) version of the weight-gradient GEMM: same 128x128 tile / 4 waves of 64x64 / interleaved
-// feature map, but a slab is 32 contraction rows = one bf16 MFMA k-step: lane (l15, q) owns rows 8q..8q+7, reads them as
-// 8 float4 per operand (4 interleaved feature tiles each), splits every value into hi + lo bf16 and issues
-// lo*hi + hi*lo + hi*hi for each of the 16 tile pairs (48 MFMAs per slab instead of 128 fp32 ones at half the rate).
+// Split-precision (bf16x3) version of the 128x128 weight-gradient GEMM: the LDS layout, ring and k-step of
+// gemm_f32_tn_lds_body<4, 3, PREC_BF16X3>, but lane (l15, q) reads all 8 of its rows (8 float4 per operand) before it splits any.
+// Run as that body instead it measured 30.1 us against 27.9 us (mean over the q/k/v, W1 and W2 weight gradients, BT = 2048, one
+// kernel trace each), so it stays a kernel of its own.  48 MFMAs per slab instead of 128 fp32 ones at half the rate.
 #define TS_ROWS 32
 #define TS_NST 3   // (4-deep measured no better)
 __global__ __launch_bounds__(256) void gemm_f32_tn_split_kernel(const float* __restrict__ dY, const float* __restrict__ X,
@@ -1703,23 +1589,19 @@ __global__ __launch_bounds__(256) void gemm_f32_tn_split_kernel(const float* __r
       a4[r] = *reinterpret_cast<const f32x4*>(cur + offA + m * 512) * keep;
       b4[r] = *reinterpret_cast<const f32x4*>(cur + offB + m * 512);
     }
-    bf16x8 bh[4], bl[4];
+    BfOp<PREC_BF16X3> bh[4];
 #pragma unroll
     for (int cb = 0; cb < 4; ++cb) {
       const float x[8] = {b4[0][cb], b4[1][cb], b4[2][cb], b4[3][cb], b4[4][cb], b4[5][cb], b4[6][cb], b4[7][cb]};
-      split_bf16x8(x, bh[cb], bl[cb]);
+      bf_pack8(bh[cb], x);
     }
 #pragma unroll
     for (int ca = 0; ca < 4; ++ca) {
       const float x[8] = {a4[0][ca], a4[1][ca], a4[2][ca], a4[3][ca], a4[4][ca], a4[5][ca], a4[6][ca], a4[7][ca]};
-      bf16x8 ah, al;
-      split_bf16x8(x, ah, al);
+      BfOp<PREC_BF16X3> ah;
+      bf_pack8(ah, x);
 #pragma unroll
-      for (int cb = 0; cb < 4; ++cb) {
-        acc[ca][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh[cb], acc[ca][cb], 0, 0, 0);
-        acc[ca][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl[cb], acc[ca][cb], 0, 0, 0);
-        acc[ca][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh[cb], acc[ca][cb], 0, 0, 0);
-      }
+      for (int cb = 0; cb < 4; ++cb) acc[ca][cb] = bf_mfma(ah, bh[cb], acc[ca][cb]);
     }
   }
   float* cp = Cp + (size_t)s * NI * NJ;
@@ -1877,6 +1759,22 @@ int check_dims(const char* fn, int B, int T, int D, int H, int M, int w) {
   return TSPO_OK;
 }
 
+// The option flags each entry takes: 0 tspo_selector_forward_ex, 1 tspo_selector_backward_ex, 2 tspo_policy_backward(_ex).
+constexpr int kSelFlags[3] = {TSPO_SEL_BF16X3 | TSPO_SEL_BF16 | TSPO_SEL_BF16_MIXED,
+                              TSPO_SEL_BF16X3 | TSPO_SEL_ACCUMULATE | TSPO_SEL_BF16_MIXED,
+                              TSPO_SEL_BF16X3 | TSPO_SEL_ACCUMULATE | TSPO_SEL_BF16_MIXED};
+
+// Validates the flags of a call to `entry` and sets *p to the GEMM precision they select.  TSPO_SEL_BF16_MIXED is TSPO_SEL_BF16's
+// arithmetic in the forward (bitwise the same scores, its workspace valid for a backward) and in both gradient GEMMs of the backward.
+int sel_prec(const char* fn, int entry, int flags, int D, Prec* p) {
+  TSPO_REQUIRE((flags & ~kSelFlags[entry]) == 0, "%s: unknown flags 0x%x", fn, flags);
+  const int pf = flags & (TSPO_SEL_BF16X3 | TSPO_SEL_BF16 | TSPO_SEL_BF16_MIXED);
+  TSPO_REQUIRE((pf & (pf - 1)) == 0, "%s: TSPO_SEL_BF16X3, TSPO_SEL_BF16 and TSPO_SEL_BF16_MIXED are exclusive (flags 0x%x)", fn, flags);
+  TSPO_REQUIRE(!(flags & TSPO_SEL_BF16) || D % 32 == 0, "%s: TSPO_SEL_BF16 needs D %% 32 == 0 (D=%d)", fn, D);
+  *p = (pf & (TSPO_SEL_BF16 | TSPO_SEL_BF16_MIXED)) ? PREC_BF16 : (pf ? PREC_BF16X3 : PREC_F32);
+  return TSPO_OK;
+}
+
 }  // namespace
 
 extern "C" size_t tspo_selector_workspace_bytes(int B, int T, int D, int H, int M, int window) {
@@ -1888,13 +1786,8 @@ static int selector_forward_impl(const tspo_selector_weights* w, const float* im
                                  const float* clip, int B, int T, int D, int H, int M, int window, float tau,
                                  float* scores, float* temporal_attn, void* workspace, size_t workspace_bytes,
                                  tspo_stream_t stream, int flags) {
-  TSPO_REQUIRE((flags & ~(TSPO_SEL_BF16X3 | TSPO_SEL_BF16 | TSPO_SEL_BF16_MIXED)) == 0, "selector_forward: unknown flags 0x%x", flags);
-  TSPO_REQUIRE((flags & (TSPO_SEL_BF16X3 | TSPO_SEL_BF16)) != (TSPO_SEL_BF16X3 | TSPO_SEL_BF16), "selector_forward: TSPO_SEL_BF16X3 and TSPO_SEL_BF16 are exclusive");
-  TSPO_REQUIRE(!(flags & TSPO_SEL_BF16_MIXED) || !(flags & (TSPO_SEL_BF16X3 | TSPO_SEL_BF16)),
-               "selector_forward: TSPO_SEL_BF16_MIXED is exclusive with TSPO_SEL_BF16X3 and TSPO_SEL_BF16");
-  TSPO_REQUIRE(!(flags & TSPO_SEL_BF16) || D % 32 == 0, "selector_forward: TSPO_SEL_BF16 needs D %% 32 == 0 (D=%d)", D);
-  // TSPO_SEL_BF16_MIXED: the forward arithmetic of TSPO_SEL_BF16 (bitwise the same scores), its workspace valid for a backward
-  const int split = (flags & (TSPO_SEL_BF16 | TSPO_SEL_BF16_MIXED)) ? 2 : ((flags & TSPO_SEL_BF16X3) ? 1 : 0);
+  Prec prec;
+  if (int e = sel_prec("selector_forward", 0, flags, D, &prec)) return e;
   TSPO_REQUIRE(w && img && txt && scores && workspace, "selector_forward: null pointer");
   TSPO_REQUIRE(w->wqkv && w->bqkv && w->w1 && w->b1 && w->w2 && w->b2, "selector_forward: null weight pointer");
   if (int e = check_dims("selector_forward", B, T, D, H, M, window)) return e;
@@ -1908,13 +1801,13 @@ static int selector_forward_impl(const tspo_selector_weights* w, const float* im
   int nb = (int)((tot / 2 + 255) / 256);
   if (nb > 4096) nb = 4096;
   hipLaunchKernelGGL(posenc_add_kernel, dim3(nb), dim3(256), 0, st, img, s.xpe, T, D, tot);
-  if (int e = launch_gemm_nt<EPI_NONE>(s.xpe, w->wqkv, w->bqkv, nullptr, s.qkv, BT, 3 * D, D, st, split)) return e;
+  if (int e = launch_gemm_nt<EPI_NONE>(s.xpe, w->wqkv, w->bqkv, nullptr, s.qkv, BT, 3 * D, D, st, prec)) return e;
   const long pairs = (long)BT * H;
   if (!band_mfma(0, s.qkv, s.ctx, s.P, nullptr, nullptr, nullptr, B, T, D, H, window, st))
     hipLaunchKernelGGL(band_attn_fwd_kernel, dim3((unsigned)((pairs + 7) / 8)), dim3(256), 0, st, s.qkv, s.ctx, s.P, B, T,
                        D, H, window);
-  if (int e = launch_gemm_nt<EPI_RELU>(s.ctx, w->w1, w->b1, nullptr, s.h1, BT, D, D, st, split)) return e;
-  if (int e = launch_gemm_nt<EPI_RESID>(s.h1, w->w2, w->b2, img, s.h2, BT, D, D, st, split)) return e;
+  if (int e = launch_gemm_nt<EPI_RELU>(s.ctx, w->w1, w->b1, nullptr, s.h1, BT, D, D, st, prec)) return e;
+  if (int e = launch_gemm_nt<EPI_RESID>(s.h1, w->w2, w->b2, img, s.h2, BT, D, D, st, prec)) return e;
   hipLaunchKernelGGL(score_fwd_kernel, dim3((BT + 3) / 4), dim3(256), 0, st, s.h2, txt, clip, scores, B, T, D, M, tau);
   if (temporal_attn) {
     hipError_t e = hipMemcpyAsync(temporal_attn, s.h2, tot * sizeof(float), hipMemcpyDeviceToDevice, st);
@@ -1947,35 +1840,38 @@ struct FinalGrad {
   float* sq = nullptr;     // one sum of squares per workgroup (or nullptr)
   int accumulate = 0;
 };
-// mode: 0 exact fp32, 1 bf16x3 (hi/lo split), 2 bf16 operands (TSPO_SEL_BF16_MIXED)
-int weight_grad(const float* dY, const float* X, float* part, float* cpart, int cstride, int BT, int NI, int NJ,
-                const SelWs& s, hipStream_t st, int mode, const FinalGrad& fin = FinalGrad()) {
+template <Prec P>
+int weight_grad_p(const float* dY, const float* X, float* part, float* cpart, int cstride, int BT, int NI, int NJ, const SelWs& s,
+                  hipStream_t st, const FinalGrad& fin) {
+  // bf16x3 has its own 128x128 kernel only: the direct-load fallback (NI or NJ not a multiple of 128) runs exact fp32 for it, and
+  // the final 64x64 form is reached from the fused backward alone, which bf16x3 does not take
+  constexpr Prec PX = P == PREC_BF16X3 ? PREC_F32 : P;
   if (fin.w) {
-    if (mode == 2)
-      hipLaunchKernelGGL(gemm_f32_tn64_kernel<1>, dim3(NJ / 64, NI / 64, 1), dim3(512), 0, st, dY, X, fin.w, fin.b, 0, fin.sq,
-                         fin.accumulate, BT, NI, NJ, (BT + 3) / 4 * 4);
-    else
-      hipLaunchKernelGGL(gemm_f32_tn64_kernel<0>, dim3(NJ / 64, NI / 64, 1), dim3(512), 0, st, dY, X, fin.w, fin.b, 0, fin.sq,
-                         fin.accumulate, BT, NI, NJ, (BT + 3) / 4 * 4);
+    hipLaunchKernelGGL(gemm_f32_tn64_kernel<PX>, dim3(NJ / 64, NI / 64, 1), dim3(512), 0, st, dY, X, fin.w, fin.b, 0, fin.sq,
+                       fin.accumulate, BT, NI, NJ, (BT + 3) / 4 * 4);
     return tspo::check_launch("selector weight_grad (64x64, final)");
   }
   const int chunk = ((BT + s.S - 1) / s.S + 3) / 4 * 4;
   dim3 grid((NJ + 127) / 128, (NI + 127) / 128, s.S);
-  if (mode == 1 && NI % 128 == 0 && NJ % 128 == 0)
+  if (NI % 128 == 0 && NJ % 128 == 0 && P == PREC_BF16X3)
     hipLaunchKernelGGL(gemm_f32_tn_split_kernel, grid, dim3(256), 0, st, dY, X, part, BT, NI, NJ, chunk);
-  else if (mode == 2 && NI % 128 == 0 && NJ % 128 == 0)
-    hipLaunchKernelGGL(gemm_f32_tn_lds_kernel<1>, grid, dim3(256), 0, st, dY, X, part, cpart, cstride, BT, NI, NJ, chunk);
-  else if (mode == 2)
-    hipLaunchKernelGGL(gemm_f32_tn_bf16_kernel, grid, dim3(256), 0, st, dY, X, part, BT, NI, NJ, chunk);
   else if (NI % 128 == 0 && NJ % 128 == 0)
-    hipLaunchKernelGGL(gemm_f32_tn_lds_kernel<0>, grid, dim3(256), 0, st, dY, X, part, cpart, cstride, BT, NI, NJ, chunk);
+    hipLaunchKernelGGL(gemm_f32_tn_lds_kernel<PX>, grid, dim3(256), 0, st, dY, X, part, cpart, cstride, BT, NI, NJ, chunk);
   else
-    hipLaunchKernelGGL(gemm_f32_tn_kernel, grid, dim3(256), 0, st, dY, X, part, BT, NI, NJ, chunk);
+    hipLaunchKernelGGL(gemm_f32_tn_kernel<PX>, grid, dim3(256), 0, st, dY, X, part, BT, NI, NJ, chunk);
   return tspo::check_launch("selector weight_grad");
+}
+int weight_grad(const float* dY, const float* X, float* part, float* cpart, int cstride, int BT, int NI, int NJ, const SelWs& s,
+                hipStream_t st, Prec p, const FinalGrad& fin = FinalGrad()) {
+  switch (p) {
+    case PREC_BF16X3: return weight_grad_p<PREC_BF16X3>(dY, X, part, cpart, cstride, BT, NI, NJ, s, st, fin);
+    case PREC_BF16: return weight_grad_p<PREC_BF16>(dY, X, part, cpart, cstride, BT, NI, NJ, s, st, fin);
+    default: return weight_grad_p<PREC_F32>(dY, X, part, cpart, cstride, BT, NI, NJ, s, st, fin);
+  }
 }
 
 // dX = mask?(dY W) together with the weight gradient dYw^T Xw of another layer in one launch (see dgrad_wgrad_kernel)
-template <int EPI, int BF>
+template <int EPI, Prec P>
 int dgrad_with_wgrad(const float* dY, const float* Wt, const float* R, float* dX, int BT, int N, int K, const float* dYw,
                      const float* Xw, float* part, float* cpart, int cstride, int NI, int NJ, const SelWs& s,
                      hipStream_t st, const FinalGrad& fin = FinalGrad()) {
@@ -1988,14 +1884,14 @@ int dgrad_with_wgrad(const float* dY, const float* Wt, const float* R, float* dX
   if (n_nt < 128 && N % 32 == 0) {
     const int n_tiles = (N / 32) * ((BT + 31) / 32), n_nt_s = (n_tiles + 1) / 2;
     if (fin.w)
-      hipLaunchKernelGGL((dgrad_wgrad_small_kernel<EPI, BF>), dim3(n_nt_s + (NI / 64) * (NJ / 64)), dim3(512), 0, st, dY, Wt, R, dX, BT, N,
+      hipLaunchKernelGGL((dgrad_wgrad_small_kernel<EPI, P>), dim3(n_nt_s + (NI / 64) * (NJ / 64)), dim3(512), 0, st, dY, Wt, R, dX, BT, N,
                          K, n_nt_s, n_tiles, dYw, Xw, fin.w, fin.b, 0, NI, NJ, (BT + 3) / 4 * 4, 1, fin.sq, fin.accumulate);
     else
-      hipLaunchKernelGGL((dgrad_wgrad_small_kernel<EPI, BF>), dim3(n_nt_s + n_tn), dim3(512), 0, st, dY, Wt, R, dX, BT, N, K, n_nt_s,
+      hipLaunchKernelGGL((dgrad_wgrad_small_kernel<EPI, P>), dim3(n_nt_s + n_tn), dim3(512), 0, st, dY, Wt, R, dX, BT, N, K, n_nt_s,
                          n_tiles, dYw, Xw, part, cpart, cstride, NI, NJ, chunk, 0, (float*)nullptr, 0);
     return tspo::check_launch("selector dgrad+wgrad");
   }
-  hipLaunchKernelGGL((dgrad_wgrad_kernel<EPI, BF>), dim3(n_nt + n_tn), dim3(512), 0, st, dY, Wt, R, dX, BT, N, K, n_nt, dYw, Xw,
+  hipLaunchKernelGGL((dgrad_wgrad_kernel<EPI, P>), dim3(n_nt + n_tn), dim3(512), 0, st, dY, Wt, R, dX, BT, N, K, n_nt, dYw, Xw,
                      part, cpart, cstride, NI, NJ, chunk);
   return tspo::check_launch("selector dgrad+wgrad");
 }
@@ -2007,12 +1903,8 @@ static int selector_backward_impl(const tspo_selector_weights* w, const float* i
                                   tspo_stream_t stream, int flags, const PgIn* pg = nullptr, float* norm_partials = nullptr,
                                   int* n_partials = nullptr) {
   const int accum = (flags & TSPO_SEL_ACCUMULATE) ? 1 : 0;
-  TSPO_REQUIRE((flags & ~(TSPO_SEL_BF16X3 | TSPO_SEL_ACCUMULATE | TSPO_SEL_BF16_MIXED)) == 0, "selector_backward: unknown flags 0x%x",
-               flags);
-  TSPO_REQUIRE((flags & (TSPO_SEL_BF16X3 | TSPO_SEL_BF16_MIXED)) != (TSPO_SEL_BF16X3 | TSPO_SEL_BF16_MIXED),
-               "selector_backward: TSPO_SEL_BF16X3 and TSPO_SEL_BF16_MIXED are exclusive");
-  // 0 exact fp32, 1 bf16x3, 2 bf16 operands (the weight-gradient and data-gradient GEMMs of TSPO_SEL_BF16_MIXED)
-  const int mode = (flags & TSPO_SEL_BF16_MIXED) ? 2 : ((flags & TSPO_SEL_BF16X3) ? 1 : 0);
+  Prec prec;
+  if (int e = sel_prec("selector_backward", pg ? 2 : 1, flags, D, &prec)) return e;
   TSPO_REQUIRE(w && img && txt && (dscores || pg) && g && workspace, "selector_backward: null pointer");
   TSPO_REQUIRE(g->wqkv && g->bqkv && g->w1 && g->b1 && g->w2 && g->b2, "selector_backward: null grad pointer");
   if (int e = check_dims("selector_backward", B, T, D, H, M, window)) return e;
@@ -2035,7 +1927,7 @@ static int selector_backward_impl(const tspo_selector_weights* w, const float* i
                        T, D, M, tau, n_score, w->w1, s.w1t, w->w2, s.w2t, PgIn{});
   // exact-fp32 (and bf16-operand) path with 128-divisible D: bias-gradient column sums come out of the weight-gradient kernels, and
   // each of the two DxD weight gradients shares a launch with the data-gradient GEMM that does not depend on it
-  const bool fused = mode != 1 && D % 128 == 0 && D % 96 == 0;
+  const bool fused = prec != PREC_BF16X3 && D % 128 == 0 && D % 96 == 0;
   const int cstride = 5 * D;
   // short contractions (the small-M forms: BT = 512, the reference's micro-batch): 64x64 weight-gradient tiles that hold the whole
   // contraction write the FINAL gradients (and their sums of squares) - no partial planes, no reduction launch
@@ -2048,26 +1940,24 @@ static int selector_backward_impl(const tspo_selector_weights* w, const float* i
     fq.w = g->wqkv; fq.b = g->bqkv; fq.sq = norm_partials ? norm_partials + 2 * t64_tiles : nullptr; fq.accumulate = accum;
   }
   if (fused) {
-    // mlp.2 data gradient (dh1) || mlp.2 weight gradient (dh2^T h1)
-    if (mode == 2) {
-      if (int e = dgrad_with_wgrad<EPI_MASK, 1>(s.dh2, s.w2t, s.h1, s.dh1, BT, D, D, s.dh2, s.h1, part_w2, s.cpart, cstride, D, D, s,
-                                                st, f2)) return e;
-      if (int e = dgrad_with_wgrad<EPI_NONE, 1>(s.dh1, s.w1t, nullptr, s.dctx, BT, D, D, s.dh1, s.ctx, part_w1, s.cpart + D,
-                                                cstride, D, D, s, st, f1)) return e;
-    } else {
-      if (int e = dgrad_with_wgrad<EPI_MASK, 0>(s.dh2, s.w2t, s.h1, s.dh1, BT, D, D, s.dh2, s.h1, part_w2, s.cpart, cstride, D, D, s,
+    auto mlp = [&](auto prec_c) -> int {
+      constexpr Prec P = decltype(prec_c)::value;
+      // mlp.2 data gradient (dh1) || mlp.2 weight gradient (dh2^T h1)
+      if (int e = dgrad_with_wgrad<EPI_MASK, P>(s.dh2, s.w2t, s.h1, s.dh1, BT, D, D, s.dh2, s.h1, part_w2, s.cpart, cstride, D, D, s,
                                                 st, f2)) return e;
       // mlp.0 data gradient (dctx) || mlp.0 weight gradient (dh1^T ctx)
-      if (int e = dgrad_with_wgrad<EPI_NONE, 0>(s.dh1, s.w1t, nullptr, s.dctx, BT, D, D, s.dh1, s.ctx, part_w1, s.cpart + D,
-                                                cstride, D, D, s, st, f1)) return e;
-    }
+      return dgrad_with_wgrad<EPI_NONE, P>(s.dh1, s.w1t, nullptr, s.dctx, BT, D, D, s.dh1, s.ctx, part_w1, s.cpart + D, cstride, D, D,
+                                           s, st, f1);
+    };
+    if (int e = prec == PREC_BF16 ? mlp(std::integral_constant<Prec, PREC_BF16>()) : mlp(std::integral_constant<Prec, PREC_F32>()))
+      return e;
   } else {
     // mlp.2
-    if (int e = weight_grad(s.dh2, s.h1, part_w2, nullptr, 0, BT, D, D, s, st, mode)) return e;
-    if (int e = launch_gemm_nt<EPI_MASK>(s.dh2, s.w2t, nullptr, s.h1, s.dh1, BT, D, D, st, mode)) return e;
+    if (int e = weight_grad(s.dh2, s.h1, part_w2, nullptr, 0, BT, D, D, s, st, prec)) return e;
+    if (int e = launch_gemm_nt<EPI_MASK>(s.dh2, s.w2t, nullptr, s.h1, s.dh1, BT, D, D, st, prec)) return e;
     // mlp.0
-    if (int e = weight_grad(s.dh1, s.ctx, part_w1, nullptr, 0, BT, D, D, s, st, mode)) return e;
-    if (int e = launch_gemm_nt<EPI_NONE>(s.dh1, s.w1t, nullptr, nullptr, s.dctx, BT, D, D, st, mode)) return e;
+    if (int e = weight_grad(s.dh1, s.ctx, part_w1, nullptr, 0, BT, D, D, s, st, prec)) return e;
+    if (int e = launch_gemm_nt<EPI_NONE>(s.dh1, s.w1t, nullptr, nullptr, s.dctx, BT, D, D, st, prec)) return e;
   }
   // banded attention
   const long pairs = (long)BT * H;
@@ -2079,7 +1969,7 @@ static int selector_backward_impl(const tspo_selector_weights* w, const float* i
     hipLaunchKernelGGL(band_attn_bwd_kv_kernel, dim3(pb), dim3(256), 0, st, s.qkv, s.P, s.dS, s.dctx, s.dqkv, B, T, D, H,
                        window);
   // q/k/v projections
-  if (int e = weight_grad(s.dqkv, s.xpe, part_qkv, fused ? s.cpart + 2 * D : nullptr, cstride, BT, 3 * D, D, s, st, mode, fq))
+  if (int e = weight_grad(s.dqkv, s.xpe, part_qkv, fused ? s.cpart + 2 * D : nullptr, cstride, BT, 3 * D, D, s, st, prec, fq))
     return e;
   if (t64) {   // every gradient is final
     if (norm_partials && n_partials) *n_partials = 5 * t64_tiles;
@@ -2120,13 +2010,10 @@ static int selector_backward_impl(const tspo_selector_weights* w, const float* i
   return tspo::check_launch("selector_backward");
 }
 
-extern "C" int tspo_selector_supported_flags(int entry) {
-  switch (entry) {   // (host only: no device is touched)
-    case 0: return TSPO_SEL_BF16X3 | TSPO_SEL_BF16 | TSPO_SEL_BF16_MIXED;
-    case 1:
-    case 2: return TSPO_SEL_BF16X3 | TSPO_SEL_ACCUMULATE | TSPO_SEL_BF16_MIXED;
-    default: return tspo::set_err(TSPO_EINVAL, "selector_supported_flags: entry %d (0 forward_ex, 1 backward_ex, 2 policy_backward)", entry);
-  }
+extern "C" int tspo_selector_supported_flags(int entry) {   // (host only: no device is touched)
+  if (entry < 0 || entry > 2)
+    return tspo::set_err(TSPO_EINVAL, "selector_supported_flags: entry %d (0 forward_ex, 1 backward_ex, 2 policy_backward)", entry);
+  return kSelFlags[entry];
 }
 
 extern "C" int tspo_policy_backward(const tspo_selector_weights* w, const float* img, const float* txt, const float* rewards,
