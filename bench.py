@@ -2,8 +2,9 @@
 """bench.py - frames scored/s (+ rollouts/s) of the TSPO temporal-sampling hot path on MI355X.
 
     python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --gpus 1 --steps 5 --warmup 2 --full   # + every non-headline measurement (see below)
     python bench.py --gpus 8                      # no launcher: spawns its own 8 ranks (one per GPU, RCCL)
-    python bench.py --gpus 8 --frames 4096 --shard-frames --rollout-cfg 1,4096,16,16   # configs[4]: ONE 4096-frame video over 8 GPUs (strong scaling)
+    python bench.py --gpus 8 --frames 4096 --shard-frames --rollout-cfg 1,4096,16,16 --full   # configs[4]: ONE 4096-frame video over 8 GPUs (strong scaling)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -11,9 +12,15 @@ Workload (BASELINE.json configs[1]): TSPO-0.4B frame selection, T=1024 synthetic
 top-k=32: pixels [B,T,3,224,224] resident in HBM -> CLIP-L/14 encode (bf16 MFMA) -> cosine clip score ->
 temporal scoring head (fp32, window 12, tau 0.025) -> greedy top-k.  One "step" = one such pass over one
 batch of B videos per GPU.  value = B*T*N*K / max-over-ranks wall time (weak scaling: videos are
-independent, no data-path collective).  Also timed: the policy side of one TSPO training step
-(configs[2]: B=4, T=512, G=8, k=16; reward LLM excluded, rewards synthetic) -> "rollouts_per_s".
-Weights are random-init tensors of the CLIP-L/14 + selector shapes (no network for checkpoints).
+independent, no data-path collective).  Weights are random-init tensors of the CLIP-L/14 + selector shapes
+(no network for checkpoints).
+
+A plain run does only what `value` needs: set up, warm up, time the steps, write --dump-outputs, print the line.
+Everything else runs with --full alone (the --no-* options skip parts of it): the policy side of one TSPO training
+step (configs[2]: B=4, T=512, G=8, k=16; reward LLM excluded, rewards synthetic) -> "rollouts_per_s", the DP-path
+and bf16x3 rollout figures, the pruned-last-block and 720p variants, the score / select split, the N > 1 sharded
+4096-frame point, the RCCL probe, the GEMM roofline with the clock / power sampled during the timed steps, and the
+CPU baseline.  Fields a plain run did not measure are null, and "full" says which kind of run printed the line.
 """
 import argparse
 import json
@@ -521,7 +528,11 @@ def dump_outputs(path: str, tensors: dict, limit: int = DUMP_LIMIT_BYTES) -> dic
     return written
 
 
-def main():
+FULL_ONLY = ("no_cpu_baseline", "no_rollouts", "no_profile", "no_pruned", "no_720p", "no_long_form", "no_comm_probe")
+
+
+def parse_args(argv=None):
+    """The command line; without --full every non-headline measurement is switched off (each FULL_ONLY option set)."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
@@ -549,9 +560,20 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="after the timed steps, write what rank 0's last timed step returned (top-k indices, scores, features) as "
                          "DIR/<name>.npy, float32 / float64, at most 64 MB in all; the inputs are seeded, so two builds compare output for output")
-    a = ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every non-headline measurement (rollouts, variants, score / select split, comm probe, roofline, "
+                         "CPU baseline); without it the --no-* options have nothing to skip")
+    a = ap.parse_args(argv)
     if a.steps < 1:
         ap.error("--steps must be at least 1")
+    if not a.full:
+        for opt in FULL_ONLY:
+            setattr(a, opt, True)
+    return a
+
+
+def main():
+    a = parse_args()
 
     if not torch.cuda.is_available():
         sys.exit("bench.py needs an MI355X (no CPU path in the product); use gpurun")
@@ -663,12 +685,14 @@ def main():
             out["idx"], out["scores"], out["feats"] = scorer(pixels, txt, k)
 
     step_ms, rank_sec = [], []
-    sampler = GpuSampler(dev)
+    sampler = GpuSampler(dev) if a.full else None      # (read by the roofline only)
     try:
-        sec = timed(score_step, a.steps, a.warmup, per_step=step_ms, after_warmup=sampler.__enter__, per_rank=rank_sec)
+        sec = timed(score_step, a.steps, a.warmup, per_step=step_ms, per_rank=rank_sec,
+                    after_warmup=sampler.__enter__ if sampler is not None else None)
     finally:
-        sampler.__exit__(None, None, None)
-    gpu_state = sampler.summary()
+        if sampler is not None:
+            sampler.__exit__(None, None, None)
+    gpu_state = sampler.summary() if sampler is not None else None
     frames = B * T * (1 if shard else world) * a.steps      # sharded: the ranks share ONE video (strong scaling)
     fps = frames / sec
     assert out["idx"].shape == (B, min(T, k)) and bool((out["idx"][:, 1:] > out["idx"][:, :-1]).all())
@@ -741,20 +765,26 @@ def main():
             long_form = {"error": f"{type(e).__name__}: {e}"[:300]}
 
     # ---- split: score + select only (features resident), SURVEY 8(d) ----------
-    feats_res = scorer.encode(pixels, shard_frames=shard)
+    split = None
+    if a.full:
+        feats_res = scorer.encode(pixels, shard_frames=shard)
 
-    def select_step():
-        sc, _ = scorer.score(feats_res, txt)
-        out["idx2"] = ops.topk_sorted(sc, k)
+        def select_step():
+            sc, _ = scorer.score(feats_res, txt)
+            out["idx2"] = ops.topk_sorted(sc, k)
 
-    sel_sec = timed(select_step, max(a.steps, 200), 3) / max(a.steps, 200)
-    assert torch.equal(out["idx2"], out["idx"])
-    # the same stage at the reference's own inference precision (gen_id_tspo.py:55 loads the scoring head in bf16): bf16 GEMM operands,
-    # fp32 accumulation (TSPO_SEL_BF16) - opt-in, NOT used for `value`; how many of the fp32 path's k indices it keeps is reported
-    scorer.selector_precision = "bf16"
-    sel16_sec = timed(select_step, max(a.steps, 200), 3) / max(a.steps, 200)
-    keep16 = sum(len(set(x) & set(y)) for x, y in zip(out["idx2"].tolist(), out["idx"].tolist())) / max(1, out["idx"].numel())
-    scorer.selector_precision = "fp32"
+        sel_sec = timed(select_step, max(a.steps, 200), 3) / max(a.steps, 200)
+        assert torch.equal(out["idx2"], out["idx"])
+        # the same stage at the reference's own inference precision (gen_id_tspo.py:55 loads the scoring head in bf16): bf16 GEMM
+        # operands, fp32 accumulation (TSPO_SEL_BF16) - opt-in, NOT used for `value`; how many of the fp32 path's k indices it keeps
+        scorer.selector_precision = "bf16"
+        sel16_sec = timed(select_step, max(a.steps, 200), 3) / max(a.steps, 200)
+        keep16 = sum(len(set(x) & set(y)) for x, y in zip(out["idx2"].tolist(), out["idx"].tolist())) / max(1, out["idx"].numel())
+        scorer.selector_precision = "fp32"
+        split = {"encode": round(sec / a.steps * 1e3 - sel_sec * 1e3, 3), "score_select": round(sel_sec * 1e3, 3),
+                 "score_select_bf16_operands": round(sel16_sec * 1e3, 3), "bf16_keeps_fraction_of_fp32_topk": round(keep16, 4),
+                 "note": "score_select = clip cosine + scoring head + top-k on resident features, exact fp32 (used for `value`); "
+                         "_bf16_operands = the same with FrameScorer(selector_precision='bf16'), the reference's inference precision"}
 
     # ---- rollouts / s (policy side of one TSPO step, configs[2]) --------------
     rollouts = rollouts_x3 = dp_path = None
@@ -836,6 +866,7 @@ def main():
             "ms_per_step_max": round(max(step_ms), 3),
             "ms_per_step_by_rank": [round(x / a.steps * 1e3, 3) for x in rank_sec],     # each rank's own clock over the timed region
             "higher_is_better": True, "scaling": "strong" if shard else "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
+            "full": a.full,
             "config": {"workload": workload_name(T, B, k, world, shard),
                        "frames_per_video": T, "videos_per_gpu_per_step": None if shard else B, "videos_per_step_total": 1 if shard else B * world,
                        "frames_per_gpu_per_step": -(-T // world) if shard else B * T, "topk": k, "window": 12, "tau": 0.025,
@@ -866,10 +897,7 @@ def main():
                         "(same features); not used for `value`"},
             "frames_scored_per_s_from_720p_u8": from_720p,
             "configs4_long_form_sharded": long_form,
-            "split_ms": {"encode": round(sec / a.steps * 1e3 - sel_sec * 1e3, 3), "score_select": round(sel_sec * 1e3, 3),
-                         "score_select_bf16_operands": round(sel16_sec * 1e3, 3), "bf16_keeps_fraction_of_fp32_topk": round(keep16, 4),
-                         "note": "score_select = clip cosine + scoring head + top-k on resident features, exact fp32 (used for `value`); "
-                                 "_bf16_operands = the same with FrameScorer(selector_precision='bf16'), the reference's inference precision"},
+            "split_ms": split,
             "roofline": roof, "cpu_baseline": cpu, "comm": comm, "dumped_outputs": dumped,
             "launcher": "torch.distributed.run" if (world > 1 and not os.environ.get("TSPO_SELF_SPAWNED")) else
                         ("self-spawn" if world > 1 else "single process"),

@@ -60,9 +60,9 @@ def _json_lines(text):
 
 
 def test_bench_self_spawns_two_ranks_from_a_bare_shell():
-    """The command form the driver uses for N=1, with N=2 and no launcher environment."""
+    """The command form the driver uses for N=1, with N=2 and no launcher environment (--full: rollouts, long-form point, comm)."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--same-device", "--backend", "gloo",
-                        "--frames", "64", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-pruned"],
+                        "--frames", "64", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-pruned"],
                        env=_clean_env(), cwd=ROOT, capture_output=True, text=True, timeout=900)
     _ok(r, "bench_self_spawn_2ranks")
     lines = [l for l in _json_lines(r.stdout) if "metric" in l]
@@ -70,7 +70,7 @@ def test_bench_self_spawns_two_ranks_from_a_bare_shell():
     line = lines[0]
     assert line["n_gpus"] == 2 and line["launcher"] == "self-spawn" and line["config"]["parallelism"] == "dp2"
     assert line["value"] > 0 and line["rollouts_per_s"] > 0 and line["steps"] == 2
-    lf = line["configs4_long_form_sharded"]            # N > 1: the strong-scaling point of configs[4] rides in the default launch
+    lf = line["configs4_long_form_sharded"]            # N > 1: the strong-scaling point of configs[4] rides in the --full launch
     assert lf and "error" not in lf and lf["frames_per_video"] == 4096 and lf["frames_per_gpu"] == 2048 and lf["frames_scored_per_s"] > 0
     assert lf["scaling"] == "strong" and lf["workload"].startswith("configs[4] long-form option")
     by_rank = line["ms_per_step_by_rank"]             # every rank's own clock over the timed region: a slow rank must be visible
@@ -86,8 +86,8 @@ def test_bench_shard_frames_two_ranks_strong_scaling_line():
     all-gather): a STRONG-scaling line (value counts the ONE video's frames, not frames x ranks), the workload named from
     the arguments, every rank encoding half of the frames (that the sharded features equal the single-process ones bit for
     bit is test_frame_sharded_encode_real_encoder_two_ranks below); and the unsharded line of the same size for comparison."""
-    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--frames", "128", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
-            "--no-pruned", "--no-720p", "--no-rollouts", "--no-comm-probe"]
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--frames", "128", "--steps", "2", "--warmup", "1", "--full",
+            "--no-cpu-baseline", "--no-pruned", "--no-720p", "--no-rollouts", "--no-comm-probe"]
     r = subprocess.run(base + ["--gpus", "2", "--same-device", "--backend", "gloo", "--shard-frames"],
                        env=_clean_env(), cwd=ROOT, capture_output=True, text=True, timeout=900)
     _ok(r, "bench_shard_frames_2ranks")
@@ -113,7 +113,7 @@ def test_bench_under_torch_distributed_run():
     for n, extra in ((2, ["--same-device", "--backend", "gloo"]), (1, [])):
         r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr",
                             "127.0.0.1", "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"), "--gpus", str(n),
-                            "--frames", "64", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-pruned", "--no-720p"] + extra,
+                            "--frames", "64", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-pruned", "--no-720p"] + extra,
                            env=_clean_env(), cwd=ROOT, capture_output=True, text=True, timeout=900)
         _ok(r, "bench_torchrun")
         lines = [l for l in _json_lines(r.stdout) if "metric" in l]
@@ -349,11 +349,11 @@ def test_self_spawn_quotes_the_failing_ranks_stderr(tmp_path):
 
 
 def test_bench_line_explains_itself_and_times_the_dp_path():
-    """The default single-GPU bench line (short run): per-step spread, the clock / power sampled during the timed steps with the
+    """The --full single-GPU bench line (short run): per-step spread, the clock / power sampled during the timed steps with the
     roofline fraction at that clock, and `rollouts_dp_path` - the reference's own training configuration (one prompt per
     micro-step, two micro-steps, the bucket all-reduce really issued on a live one-rank RCCL group) with its launch count."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
-                        "--no-pruned", "--no-720p"], env=_clean_env(), cwd=ROOT, capture_output=True, text=True, timeout=900)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--full",
+                        "--no-cpu-baseline", "--no-pruned", "--no-720p"], env=_clean_env(), cwd=ROOT, capture_output=True, text=True, timeout=900)
     _ok(r, "bench_default_line")
     line = [l for l in _json_lines(r.stdout) if "metric" in l][0]
     assert line["ms_per_step_min"] <= line["ms_per_step_median"] <= line["ms_per_step_max"]
@@ -389,6 +389,24 @@ def test_bench_line_explains_itself_and_times_the_dp_path():
     comm = line["comm"]
     assert comm["world"] == 1 and comm["backend"] == "nccl" and comm["sum_correct"] and comm["distinct_devices"] == 1
     assert comm["ranks"][0]["pci"] == roof["gpu_state"]["pci"]
+
+
+def test_plain_bench_run_times_the_headline_only():
+    """Without --full, bench.py sets up, warms up, times the steps and prints the line: the headline fields as a --full run has
+    them, every non-headline measurement null."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--frames", "64", "--topk", "8", "--steps", "3", "--warmup", "1"],
+                       env=_clean_env(), cwd=ROOT, capture_output=True, text=True, timeout=900)
+    _ok(r, "bench_plain_line")
+    lines = [l for l in _json_lines(r.stdout) if "metric" in l]
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = lines[0]
+    assert line["full"] is False and line["metric"] == "frames_scored_per_s" and line["unit"] == "frames/s"
+    assert line["higher_is_better"] is True and line["dtype"] == "bf16" and line["steps"] == 3 and line["warmup"] == 1
+    assert abs(line["value"] - 64 * 3 / (line["ms_per_step"] * 3e-3)) < 1e-2 * line["value"]
+    assert line["ms_per_step_min"] <= line["ms_per_step_median"] <= line["ms_per_step_max"]
+    for key in ("rollouts_per_s", "rollouts_dp_path", "optional_rollouts_per_s_bf16x3", "optional_pruned_last_block",
+                "frames_scored_per_s_from_720p_u8", "configs4_long_form_sharded", "split_ms", "roofline", "cpu_baseline", "comm"):
+        assert line[key] is None, key
 
 
 def test_bench_dump_outputs_of_the_last_timed_step(tmp_path):

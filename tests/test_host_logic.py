@@ -246,6 +246,18 @@ def test_bench_accounting_helpers():
     assert abs(r["achieved"] - 28.99e9 / 4e-4 / 1e12) < 0.1 and abs(r["frac"] - r["achieved"] / 157.3) < 1e-3
 
 
+def test_bench_plain_run_switches_every_non_headline_part_off():
+    """bench.py without --full measures the headline alone: every option that skips a non-headline part is set; with --full
+    they are as given.  (--no-ln-fold is an A/B of the headline path itself, not a part that can be skipped.)"""
+    import bench
+    plain = bench.parse_args(["--steps", "3", "--warmup", "1"])
+    assert plain.full is False and all(getattr(plain, o) is True for o in bench.FULL_ONLY)
+    assert set(bench.FULL_ONLY) == {o for o in vars(plain) if o.startswith("no_")} - {"no_ln_fold"}
+    assert plain.no_ln_fold is False and plain.steps == 3 and plain.warmup == 1
+    full = bench.parse_args(["--full", "--no-pruned"])
+    assert full.full is True and [o for o in bench.FULL_ONLY if getattr(full, o)] == ["no_pruned"]
+
+
 def test_reproduce_published_idx_tool_host_logic():
     """tools/reproduce_published_idx.py (local weights + videos -> FrameIdGenerator -> compare against the published lists): its
     GPU / decord branch cannot run here; the doc -> (join key, video file, problem text) mapping can, on docs shaped like the

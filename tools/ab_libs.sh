@@ -10,7 +10,7 @@ cp tspo_amd/libtspo_hip.so tmp_ab/.lib_shipped.so
 for round in $(seq 1 ${ROUNDS:-2}); do
   for v in "$@"; do
     cp tmp_ab/lib_$v.so tspo_amd/libtspo_hip.so
-    timeout 600 python bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-rollouts --no-pruned --no-720p --no-comm-probe | python -c "
+    timeout 600 python bench.py --steps 8 --warmup 2 --full --no-cpu-baseline --no-rollouts --no-pruned --no-720p --no-comm-probe | python -c "
 import json,sys; j=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=j['roofline']; b=r['breakdown_ms']
 print('%-8s round $round: %8.1f frames/s  step %7.3f ms (min %7.3f)  GEMM %6.1f TFLOP/s %7.2f ms  attn %6.3f ms  other %5.2f ms  sclk %6.1f MHz  %6.1f W' % ('$v', j['value'], j['ms_per_step'], j['ms_per_step_min'], r['achieved'], b['gemm_ms'], b['attn_ms'], b['total_ms']-b['gemm_ms']-b['attn_ms'], r.get('sclk_mhz') or 0, r.get('power_w') or 0))"
   done

@@ -9,7 +9,7 @@ ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/$TAG
 export PYTHONPATH=$ROOT TMPDIR=/tmp
 rm -rf $OUT && mkdir -p $OUT
-BENCH="python $ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-pruned"
+BENCH="python $ROOT/bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-pruned"
 (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/kt -- $BENCH > $OUT/bench_under_rocprof.json 2> $OUT/kt.err)
 python tools/rocpd_summary.py $(find $OUT/kt -name "*.db" | head -1) > $OUT/kernel_trace.txt
 head -12 $OUT/kernel_trace.txt
