@@ -396,8 +396,7 @@ int tspo_clip_scores(const float* txt, const float* feat, int B, int T, int D, i
  * Bits 8+ of `act` choose the kernel: 0 = automatic (what the encoder uses: 77 for big shapes, else 1), 1 = small-problem
  * 128x128 kernel, 77 = persistent 256x256 kernel with LDS-DMA operands (whole rounds of whole tiles + the 64x64 remainder
  * phase), 83 = the same kernel with the remainder phase off (a partial last round of whole tiles; bit-identical with 77).
- * Every choice computes the same result.  Other values (67-76 schedule A/Bs and probes, 82 = the register-staged kernel of
- * rounds 2-3) exist only in a `python -m tspo_amd.build --dev` library and are rejected with TSPO_EINVAL by the shipped one. */
+ * Every choice computes the same result.  Any other value is rejected with TSPO_EINVAL before any device work. */
 int tspo_gemm_bf16(const void* A, const void* W, const float* bias, const void* residual,
                    void* C, int out_dtype, int M, int N, int K, int act, tspo_stream_t stream);
 

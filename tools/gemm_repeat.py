@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Race screen for a GEMM variant: the same launch repeated back to back must give bitwise identical outputs.
-    python tools/gemm_repeat.py variants [repeats]      e.g.  77,73,82 12"""
+    python tools/gemm_repeat.py variants [repeats]      e.g.  77,83 12"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

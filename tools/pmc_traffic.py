@@ -8,7 +8,7 @@ Round 6: the summary is BOUND to the binary it was taken on (`library`: sha256 o
 tspo_amd.build.lib_identity) - bench.py only quotes a traffic file whose identity matches the library it loaded - and every
 form is put next to ITS algorithmic bytes (`forms`: operands read once, output written once, for the frame count given).
 Usage: pmc_traffic.py fetch.csv write.csv kernel_substring [out.json] [n_frames]"""
-import csv, json, os, sys, collections
+import csv, json, os, re, sys, collections
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -65,7 +65,7 @@ def main():
         if sub not in key[0]:
             continue
         fv, wv = fa[key], wa.get(key, [0.0])
-        rows.append({"kernel": key[0][:70], "grid": key[1], "launches": len(fv), "form": key[0].split("gemm_bf16_a9_kernel<")[-1].split(",")[0].strip(),
+        rows.append({"kernel": key[0][:70], "grid": key[1], "launches": len(fv), "form": re.split(r"[,>]", key[0].split("gemm_bf16_a9_kernel<")[-1])[0].strip(),
                      "fetch_MB_per_launch_raw": sum(fv) / len(fv) * 1024 / 1e6,
                      "fetch_MB_per_launch_x2": 2 * sum(fv) / len(fv) * 1024 / 1e6,
                      "write_MB_per_launch_raw": sum(wv) / len(wv) * 1024 / 1e6})

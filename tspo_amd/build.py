@@ -11,8 +11,8 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libtspo_hip.so")
 SOURCES = ["sampler.hip", "selector.hip", "gemm_bf16.hip", "gemm_dma.hip", "clip_vit.hip", "preprocess.hip"]
-HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_bf16.h"), os.path.join(CSRC, "gemm_epilogue.h"), os.path.join(CSRC, "gemm_agpr_common.h"),
-           os.path.join(CSRC, "gemm_dma_kernel.h"), os.path.join(os.path.dirname(PKG), "include", "tspo_hip.h")]
+HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_bf16.h"), os.path.join(CSRC, "gemm_epilogue.h"),
+           os.path.join(os.path.dirname(PKG), "include", "tspo_hip.h")]
 
 
 def _hipcc() -> str:
@@ -22,8 +22,8 @@ def _hipcc() -> str:
     raise RuntimeError("hipcc not found (set HIPCC)")
 
 
-# The hand-placed wait states around inline-asm MFMAs (csrc/gemm_epilogue.h: `s_nop 3` in front, `s_nop 15; s_nop 7` behind) and the
-# literal-AGPR kernels were validated with THIS compiler; hipcc's hazard recogniser does not see MFMAs inside asm, and how it
+# The hand-placed wait states around inline-asm MFMAs (csrc/gemm_epilogue.h, csrc/gemm_dma.hip: `s_nop 3` in front, `s_nop 15; s_nop 7`
+# behind) and the literal-AGPR kernel of csrc/gemm_dma.hip were validated with THIS compiler; hipcc's hazard recogniser does not see MFMAs inside asm, and how it
 # materialises their operand tuples may change with the version or with extra flags.  A different toolchain is not an
 # error, but it must pass the post-build checks before its library is trusted:
 #   python -m pytest tests/test_abi.py -k "code_audit or dev_hooks"          (generated-code audit: no VALU write of an MFMA operand
@@ -50,42 +50,23 @@ def toolchain_note(hipcc: str, flags) -> str:
             "before trusting this library")
 
 
-DEV_SOURCES = ["dev/gemm_dma_lab.hip", "dev/gemm_agpr.hip"]      # compiled into the library only by build(dev=True) / `--dev`
-DEV_HEADERS = [os.path.join(CSRC, "dev", "gemm_dma_lab_kernel.h")]
-MODE_STAMP = LIB + ".mode"      # "product" | "dev": which build the .so on disk is (a dev library must never pass for the shipped one)
-
-
-def built_mode():
-    try:
-        return open(MODE_STAMP).read().strip()
-    except OSError:
-        return None
-
-
-def needs_build(dev: bool = False) -> bool:
-    if not os.path.exists(LIB) or built_mode() != ("dev" if dev else "product"):
+def needs_build() -> bool:
+    if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, s) for s in SOURCES] + HEADERS
-    if dev:
-        deps += [os.path.join(CSRC, s) for s in DEV_SOURCES] + DEV_HEADERS
-    return any(os.path.getmtime(d) > t for d in deps)
+    return any(os.path.getmtime(d) > t for d in [os.path.join(CSRC, s) for s in SOURCES] + HEADERS)
 
 
-def build(force: bool = False, verbose: bool = True, dev: bool = False, only=None) -> str:
-    """The translation units compile in parallel (one hipcc per source).  dev=True links the laboratory units of csrc/dev/
-    in as well (GEMM schedule A/Bs, a timing-only ablation, the K-step probe - what tools/probe_gemm_dma.py and the A/B
-    variants of tools/bench_gemm.py need); the product sources themselves carry no conditional code and the shipped library
-    is built WITHOUT them (tests/test_abi.py checks the binary).  only=[...] recompiles just those sources and relinks with
-    the other objects as they are."""
-    if not force and not needs_build(dev):
+def build(force: bool = False, verbose: bool = True, only=None) -> str:
+    """The translation units compile in parallel (one hipcc per source).  only=[...] recompiles just those sources and
+    relinks with the other objects as they are."""
+    if not force and not needs_build():
         return LIB
     hipcc = _hipcc()
     flags = os.environ.get("TSPO_EXTRA_HIPCC_FLAGS", "").split()
     note = toolchain_note(hipcc, flags)
     if note:
         print(note, file=sys.stderr, flush=True)
-    sources = SOURCES + (DEV_SOURCES if dev else [])
 
     def compile_one(s):
         o = os.path.join(CSRC, s.replace(".hip", ".o"))
@@ -99,14 +80,12 @@ def build(force: bool = False, verbose: bool = True, dev: bool = False, only=Non
         return o
 
     from concurrent.futures import ThreadPoolExecutor
-    with ThreadPoolExecutor(max_workers=min(len(sources), os.cpu_count() or 1)) as ex:
-        objs = list(ex.map(compile_one, sources))
+    with ThreadPoolExecutor(max_workers=min(len(SOURCES), os.cpu_count() or 1)) as ex:
+        objs = list(ex.map(compile_one, SOURCES))
     cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs
     if verbose:
         print(" ".join(cmd), flush=True)
     subprocess.check_call(cmd)
-    with open(MODE_STAMP, "w") as f:
-        f.write("dev\n" if dev else "product\n")
     return LIB
 
 
@@ -123,11 +102,11 @@ def lib_identity() -> dict:
             with open(q, "rb") as f:
                 h.update(f.read())
         return h.hexdigest()
-    return {"lib_sha256": sha([LIB]) if os.path.exists(LIB) else None, "mode": built_mode(),
+    return {"lib_sha256": sha([LIB]) if os.path.exists(LIB) else None,
             "src_sha256": sha(sorted([os.path.join(CSRC, s) for s in SOURCES] + HEADERS))}
 
 
 if __name__ == "__main__":
     only = [a.split("=", 1)[1].split(",") for a in sys.argv if a.startswith("--only=")]
-    build(force=bool(only) or "--force" in sys.argv, dev="--dev" in sys.argv, only=only[0] if only else None)
+    build(force=bool(only) or "--force" in sys.argv, only=only[0] if only else None)
     print(LIB)

@@ -1,13 +1,11 @@
 // bf16 MFMA GEMMs of the CLIP encoder for gfx950 (MI355X): C = A * W^T with fused epilogues.
 // This file: the small-problem kernel (128x128x64, 2-stage LDS-DMA ring; projections, class-token rows, tiny models) and the
 // dispatcher.  Large problems (M*N >= 256^3, K >= 128) run on the persistent 256x256x64 four-wave kernel with AGPR accumulators and
-// LDS-DMA operands of gemm_dma.hip (production since round 4).  The register-staged kernel of rounds 2-3 lives in dev/gemm_agpr.hip
-// (variant 82 of a --dev build); the 8-wave ring kernel of rounds 1-2 and the round-1..3 A/B kernels are gone from the tree (their
-// measurements: DESIGN 4.1-4.3, profiles/r1_* .. r3_*; their code: git history up to 99eb127).
+// LDS-DMA operands of gemm_dma.hip (production since round 4).  The 8-wave ring kernel of rounds 1-2 and the round-1..3 A/B kernels
+// are gone from the tree (their measurements: DESIGN 4.1-4.3, profiles/r1_* .. r3_*; their code: git history up to 99eb127), and so
+// is the laboratory of rounds 2-5 - the register-staged kernel of rounds 2-3, the schedule A/Bs and probes of the LDS-DMA kernel
+// (profiles/r2_* .. r4_*; git history up to 849d8b5).
 #include "gemm_epilogue.h"
-
-// defined only by csrc/dev/gemm_agpr.hip (`python -m tspo_amd.build --dev`)
-extern "C" __attribute__((weak)) int tspo_lab_gemm_agpr(int epi, const GemmArgs* g, hipStream_t st);
 
 namespace {
 
@@ -158,33 +156,26 @@ int launch_gemm_v1(GemmArgs g, hipStream_t st) {
 }
 
 
-// Kernel for "big" problems (gemm_bf16_is_big; K is a multiple of 64 at the ABI and at least 128 here): the four-wave AGPR
-// kernel with LDS-DMA operands of gemm_dma.hip (variant 77; 83 = without its remainder phase, for A/B runs).  Variant 1 = the
-// small-problem kernel above; 82 = the register-staged kernel of rounds 2-3, present only in a --dev build (weak symbol, null
-// in the shipped library).  The shipped library reads no environment variables.
-template <int EPI>
-int launch_big(GemmArgs g, hipStream_t st) {
-  if (g.variant == 0) g.variant = 77;
-  if ((g.variant >= 67 && g.variant < 78) || g.variant == 83) return tspo::gemm_bf16_dma(EPI, g, st);
-  if (g.variant == 82 && tspo_lab_gemm_agpr) return tspo_lab_gemm_agpr(EPI, &g, st);
-  return tspo::set_err(TSPO_EINVAL, "gemm: kernel variant %d is not part of this build", g.variant);
-}
-
+// The kernel choice (GemmArgs::variant = act >> 8 of tspo_gemm_bf16), decoded here and nowhere else, before any device work:
+//   0  = automatic: the persistent kernel for big problems (gemm_bf16_is_big), the small-problem kernel above otherwise
+//   1  = the small-problem kernel (not for the LayerNorm-folded epilogues)
+//   77 = the persistent 256x256 four-wave kernel with LDS-DMA operands of gemm_dma.hip
+//   83 = the same kernel with its remainder phase off (the bitwise reference for that phase)
+// Every choice computes the same result; any other value is rejected.  The shipped library reads no environment variables.
 template <int EPI>
 int launch_gemm(GemmArgs g, hipStream_t st) {
+  constexpr bool LN = EPI == GE_BIAS_LN || EPI == GE_GELU_LN || EPI == GE_BIAS_LN_HM || EPI == GE_RESID_ST;
   const bool big = tspo::gemm_bf16_is_big(g.M, g.N, g.K);
-  if (g.variant == 1 || (g.variant == 0 && !big)) return launch_gemm_v1<EPI>(g, st);
-  return launch_big<EPI>(g, st);
-}
-
-// LayerNorm-folded epilogues exist only in the persistent 256x256 kernels
-template <int EPI>
-int launch_gemm_ln(GemmArgs g, hipStream_t st) {
-  if (!tspo::gemm_bf16_is_big(g.M, g.N, g.K) || g.N % 64)
-    return tspo::set_err(TSPO_EINVAL, "gemm: LayerNorm-folded epilogue %d needs the 256x256 kernel (M=%d N=%d K=%d)", EPI, g.M, g.N, g.K);
-  if (EPI == GE_RESID_ST ? !g.spart : !(g.lnc && g.rstats))
-    return tspo::set_err(TSPO_EINVAL, "gemm: epilogue %d without its statistics pointers", EPI);
-  return launch_big<EPI>(g, st);
+  if (LN) {   // LayerNorm-folded epilogues (and the statistics they read) exist only in the persistent 256x256 kernel
+    if (!big || g.N % 64)
+      return tspo::set_err(TSPO_EINVAL, "gemm: LayerNorm-folded epilogue %d needs the 256x256 kernel (M=%d N=%d K=%d)", EPI, g.M, g.N, g.K);
+    if (EPI == GE_RESID_ST ? !g.spart : !(g.lnc && g.rstats))
+      return tspo::set_err(TSPO_EINVAL, "gemm: epilogue %d without its statistics pointers", EPI);
+  }
+  if constexpr (!LN)
+    if (g.variant == 1 || (g.variant == 0 && !big)) return launch_gemm_v1<EPI>(g, st);
+  if (g.variant == 0 || g.variant == 77 || g.variant == 83) return tspo::gemm_bf16_dma(EPI, g, st);
+  return tspo::set_err(TSPO_EINVAL, "gemm: kernel variant %d is not part of this build", g.variant);
 }
 }  // namespace
 
@@ -194,10 +185,10 @@ bool tspo::gemm_bf16_is_big(long M, int N, int K) {
 
 int tspo::gemm_bf16(int epi, const GemmArgs& g, hipStream_t st) {
   switch (epi) {
-    case GE_BIAS_LN: return launch_gemm_ln<GE_BIAS_LN>(g, st);
-    case GE_GELU_LN: return launch_gemm_ln<GE_GELU_LN>(g, st);
-    case GE_BIAS_LN_HM: return launch_gemm_ln<GE_BIAS_LN_HM>(g, st);
-    case GE_RESID_ST: return launch_gemm_ln<GE_RESID_ST>(g, st);
+    case GE_BIAS_LN: return launch_gemm<GE_BIAS_LN>(g, st);
+    case GE_GELU_LN: return launch_gemm<GE_GELU_LN>(g, st);
+    case GE_BIAS_LN_HM: return launch_gemm<GE_BIAS_LN_HM>(g, st);
+    case GE_RESID_ST: return launch_gemm<GE_RESID_ST>(g, st);
     case GE_BIAS: return launch_gemm<GE_BIAS>(g, st);
     case GE_GELU: return launch_gemm<GE_GELU>(g, st);
     case GE_RESID: return launch_gemm<GE_RESID>(g, st);

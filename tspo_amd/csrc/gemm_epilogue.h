@@ -1,4 +1,4 @@
-// Internal: epilogue pieces shared by the bf16 GEMM kernels (gemm_bf16.hip, gemm_agpr.hip).
+// Internal: epilogue pieces shared by the bf16 GEMM kernels (gemm_bf16.hip, gemm_dma.hip).
 #pragma once
 #include "gemm_bf16.h"
 
