@@ -8,6 +8,7 @@ import torch
 from inputs import (SELECTOR_CASES, GUMBEL_CASES, TRAIN_CASES, CLIP_CASES, ENCODE_SCENARIOS, selector_inputs, gumbel_logits,
                     train_inputs, clip_pixels)
 from oracle import tspo_oracle as O
+import _clip_stages
 from tspo_amd import ops, synth
 
 pytestmark = pytest.mark.gpu
@@ -874,8 +875,7 @@ def test_residual_statistics_epilogue_against_the_stored_rows(n_frames, offset):
     significands), so a slice whose values sit near a common offset shares ONE exponent, its 64 squares are 16-bit numbers on a
     common grid and their fp32 sums are EXACT; what is left is the rounding of the one product sum x . mean (2^-24 of sum x^2).
     Asserted: |M2 - ref| <= 4e-7 x sum x^2 per slice, the merged row variance within 1e-3 (measured on MI355X: both EXACT, 0.0 and
-    1.7e-15).  Workspace layout: clip_carve() of
-    csrc/clip_vit.hip (the folded weights of all layers | x | h | qkv | a | u | patches | pooled | stats | spart, 256-byte aligned)."""
+    1.7e-15).  Workspace layout: tests/_clip_stages.py (mirror of clip_carve() in csrc/clip_vit.hip)."""
     cfg = dict(synth.CLIP_L14)
     cfg["layers"] = 1
     state = synth.clip_vision_state(**cfg)
@@ -887,21 +887,10 @@ def test_residual_statistics_epilogue_against_the_stored_rows(n_frames, offset):
     u8 = G_(synth.uniform_u8((n_frames, 3, 224, 224), 5 + n_frames))
     feat = ops.clip_vit_forward(W, u8, fold_layernorm=True)
     torch.cuda.synchronize()
-    M, C, mlp = n_frames * 257, cfg["hidden"], cfg["mlp"]
-    off = [0]
-
-    def take(nbytes):
-        o = (off[0] + 255) // 256 * 256
-        off[0] = o + nbytes
-        return o
-    Lf = cfg["layers"]
-    take(Lf * 3 * C * C * 2); take(Lf * mlp * C * 2); take(Lf * 3 * C * 4); take(Lf * 3 * C * 4); take(Lf * mlp * 4); take(Lf * mlp * 4)
-    ox = take(M * C * 2); take(M * C * 2); take(M * 3 * C * 2); take(M * C * 2); take(M * mlp * 2)
-    take(n_frames * 256 * 640 * 2); take(n_frames * C * 2); take(M * 2 * 4)
-    osp = take(M * (C // 64) * 2 * 4)
-    ws = W.workspace(n_frames)
-    x = ws[ox:ox + M * C * 2].view(torch.bfloat16).view(M, C).float()
-    sp = ws[osp:osp + M * (C // 64) * 8].view(torch.float32).view(M, C // 64, 2)
+    M, C = n_frames * 257, cfg["hidden"]
+    v = _clip_stages.views(W, n_frames)          # the workspace by name (layout checked against tspo_clip_workspace_bytes)
+    x = v["x"].float()
+    sp = v["spart"]
     assert torch.isfinite(feat).all() and torch.isfinite(x).all() and torch.isfinite(sp).all()
     xs = x.double().view(M, C // 64, 64)
     mean = xs.mean(-1)

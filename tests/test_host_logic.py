@@ -306,3 +306,17 @@ def test_batch_meta_is_per_prompt_stacked_or_not():
     reward(torch.zeros(2, 3, 2, dtype=torch.long), st)
     reward(torch.zeros(1, 3, 2, dtype=torch.long), a)
     assert seen == [[{"path": "a.pth"}, {"path": "b.pth"}], [{"path": "a.pth"}]]
+
+
+@pytest.mark.parametrize("cfg,frames", [(synth.CLIP_L14, (1, 63, 64, 70, 1024)), (dict(hidden=768, layers=12, heads=12, mlp=3072, patch=16, image=224, proj=512), (1, 111, 112)),
+                                        (synth.CLIP_TINY, (1, 3)), (dict(synth.CLIP_L14, layers=0), (5,))],
+                         ids=["clip_l14", "vit_b16", "clip_tiny", "no_layers"])
+def test_clip_workspace_layout_mirror_matches_the_library(cfg, frames):
+    """tests/_clip_stages.carve() - the names under which the GPU stage tests read the encoder's workspace - adds up to
+    tspo_clip_workspace_bytes for the configuration (pure host code of the library: no GPU needed), so a layout change in
+    clip_carve() fails here instead of making those tests read the wrong bytes."""
+    import _clip_stages
+    for n in frames:
+        lay = _clip_stages.assert_layout_matches_library(cfg, n)
+        offs = [v[0] for k, v in lay.items() if k != "__total__"]
+        assert offs == sorted(offs) and all(o % 256 == 0 for o in offs) and len(offs) == 15
