@@ -384,6 +384,34 @@ int tspo_preprocess_frames_ex(const uint8_t* frames, int layout, int T, int H, i
                               const int8_t* mfma_taps, const int32_t* mfma_bias, const int32_t* mfma_xs,
                               int mfma_nkb, int mfma_span);
 
+/* Indexed, normalising form of the two entries above: the image processor of the video-LLM applied to the frames a rollout
+ * SELECTED, without gathering them first.  Replaces
+ *   video_inputs[0][ts_ids[1].cpu()]                                   src/open_tspo/trainer/tspo_trainer.py:516
+ *   image_processor.preprocess(...)["pixel_values"].to(device).to(dtype)                        tspo_trainer.py:524
+ *   resize -> rescale -> normalize                  llava/model/multimodal_encoder/siglip_encoder.py:47-61
+ * and, through an index plan, the haystack gather in front of the CLIP front end (tspo_trainer.py:479-480,498).
+ * pool: uint8 [P,H,W,3] (layout 0) or [P,3,H,W] (layout 1).  index: int64 [N] ON THE DEVICE (e.g. straight from
+ * tspo_gumbel_topk; no host copy, no synchronisation), any order, repeats allowed; output frame n is pool frame index[n];
+ * index == NULL means 0..P-1 and needs N == P.  A value outside [0, P) is CLAMPED to the nearest valid frame - nothing
+ * outside the pool is read, nothing traps - and *oob_flag (device int32, nullable; the caller zeroes it) is set to 1.
+ * Tap / bound / matrix-pass tables, [ylo, ylo+nrows) and the choice of horizontal pass exactly as for
+ * tspo_preprocess_frames_ex (they describe geometry only: out_h != out_w, up-scaling and a window that is the whole resized
+ * image are ordinary cases).  out: [N,3,out_h,out_w] of out_dtype.  TSPO_U8: the Pillow-exact bytes u (what
+ * tspo_preprocess_frames_ex writes for the gathered frames).  TSPO_F32 / TSPO_BF16 / TSPO_F16: (u * rescale - mean[c]) / std[c],
+ * evaluated in the epilogue of the vertical pass as ONE fp32 fma u * a[c] + b[c] with a = rescale / std[c], b = -mean[c] / std[c]
+ * (divided in double, rounded once to fp32), then rounded once (to nearest even) to the narrow type: no uint8 or fp32 image
+ * goes through memory.  mean3 / std3: HOST arrays of 3 doubles (ignored for TSPO_U8); std == 0 -> TSPO_EINVAL.
+ * out must be aligned to 4 output elements (16 bytes serve every type); workspace >= tspo_preprocess_workspace_bytes(N, nrows,
+ * out_w) - sized by N, not P.                                                                                               */
+int tspo_preprocess_select(const uint8_t* pool, int layout, int P, int H, int W, const int64_t* index, int N,
+                           const int32_t* hcoef, const int32_t* hbound, int out_w, int hk,
+                           const int32_t* vcoef, const int32_t* vbound, int out_h, int vk,
+                           int ylo, int nrows, void* out, int out_dtype,
+                           double rescale, const double* mean3, const double* std3, int32_t* oob_flag,
+                           void* workspace, size_t workspace_bytes, tspo_stream_t stream,
+                           const int8_t* mfma_taps, const int32_t* mfma_bias, const int32_t* mfma_xs,
+                           int mfma_nkb, int mfma_span);
+
 /* torch.nn.CosineSimilarity(dim=-1)(text[b,0,:], feat[b,t,:])  (temporal_agent.py:167).
  * txt f32 [B,M,D] (row 0 of each prompt is used), feat f32 [B,T,D] -> clip f32 [B,T]. */
 int tspo_clip_scores(const float* txt, const float* feat, int B, int T, int D, int M, float* clip,

@@ -23,28 +23,80 @@ __device__ __forceinline__ uint32_t clip8(int v) {
   return (uint32_t)r;
 }
 
+// tspo_preprocess_select: output frame n is pool frame index[n] (int64, read on the device; NULL = n).  A value outside
+// [0, P) is clamped to the nearest valid frame - nothing outside the pool is ever addressed - and, when the caller passed a
+// flag word, reported there (benign race: every writer stores 1).
+template <bool IDX>
+__device__ __forceinline__ size_t pp_src_frame(const int64_t* __restrict__ index, size_t n, int P, int* __restrict__ flag) {
+  if (!IDX) return n;
+  long long v = index[n];
+  if (v < 0 || v >= (long long)P) {
+    if (flag) *flag = 1;
+    v = v < 0 ? 0 : (long long)P - 1;
+  }
+  return (size_t)v;
+}
+
+// Epilogue of the vertical pass.  TSPO_U8: the Pillow-exact byte.  Float types: (u * rescale - mean[c]) / std[c] as ONE fp32 fma
+// u * a[c] + b[c] with a = rescale / std and b = -mean / std divided in double on the host and rounded once to fp32; the fma rounds
+// once, the narrow types round that fp32 value once more (to nearest even).
+struct pp_norm { float a0, a1, a2, b0, b1, b2; };
+template <int OT>
+__device__ __forceinline__ void pp_store4(void* __restrict__ out, size_t e, uint32_t u0, uint32_t u1, uint32_t u2, uint32_t u3,
+                                          float a, float b) {
+  if constexpr (OT == TSPO_U8) {
+    *reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(out) + e) = u0 | (u1 << 8) | (u2 << 16) | (u3 << 24);
+  } else {
+    const float f0 = __builtin_fmaf((float)u0, a, b), f1 = __builtin_fmaf((float)u1, a, b),
+                f2 = __builtin_fmaf((float)u2, a, b), f3 = __builtin_fmaf((float)u3, a, b);
+    if constexpr (OT == TSPO_F32) {
+      *reinterpret_cast<float4*>(reinterpret_cast<float*>(out) + e) = make_float4(f0, f1, f2, f3);
+    } else if constexpr (OT == TSPO_BF16) {
+      *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(out) + e) = make_uint2(pack_bf16x2(f0, f1), pack_bf16x2(f2, f3));
+    } else {
+      const uint32_t h0 = __builtin_bit_cast(uint16_t, (_Float16)f0), h1 = __builtin_bit_cast(uint16_t, (_Float16)f1),
+                     h2 = __builtin_bit_cast(uint16_t, (_Float16)f2), h3 = __builtin_bit_cast(uint16_t, (_Float16)f3);
+      *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(out) + e) = make_uint2(h0 | (h1 << 16), h2 | (h3 << 16));
+    }
+  }
+}
+template <int OT>
+__device__ __forceinline__ void pp_store1(void* __restrict__ out, size_t e, uint32_t u, float a, float b) {
+  if constexpr (OT == TSPO_U8) {
+    reinterpret_cast<uint8_t*>(out)[e] = (uint8_t)u;
+  } else {
+    const float f = __builtin_fmaf((float)u, a, b);
+    if constexpr (OT == TSPO_F32) reinterpret_cast<float*>(out)[e] = f;
+    else if constexpr (OT == TSPO_BF16) reinterpret_cast<uint16_t*>(out)[e] = f32_to_bf16(f);
+    else reinterpret_cast<uint16_t*>(out)[e] = __builtin_bit_cast(uint16_t, (_Float16)f);
+  }
+}
+
 // tmp[t][c][yy][x] for yy in [0, nrows): input row ylo + yy, output column x of the crop window
+template <bool IDX>
 __global__ __launch_bounds__(256) void resample_h_kernel(const uint8_t* __restrict__ in, int layout, int T, int H, int W,
                                                          const int* __restrict__ coef, const int* __restrict__ bound,
                                                          int ow, int ksize, int ylo, int nrows,
-                                                         uint8_t* __restrict__ tmp) {
+                                                         uint8_t* __restrict__ tmp, const int64_t* __restrict__ index, int P,
+                                                         int* __restrict__ flag) {
   const size_t total = (size_t)T * nrows * ow;
   for (size_t id = (size_t)blockIdx.x * 256 + threadIdx.x; id < total; id += (size_t)gridDim.x * 256) {
     const int x = (int)(id % ow);
     const int yy = (int)((id / ow) % nrows);
     const size_t t = id / ((size_t)ow * nrows);
+    const size_t ts = pp_src_frame<IDX>(index, t, P, flag);
     const int xmin = bound[2 * x], xn = bound[2 * x + 1];
     const int* k = coef + (size_t)x * ksize;
     const int y = ylo + yy;
     int a0 = 1 << 21, a1 = 1 << 21, a2 = 1 << 21;
     if (layout == 0) {  // [T,H,W,3]
-      const uint8_t* p = in + ((t * H + y) * (size_t)W + xmin) * 3;
+      const uint8_t* p = in + ((ts * H + y) * (size_t)W + xmin) * 3;
       for (int i = 0; i < xn; ++i) {
         const int w = k[i];
         a0 += __mul24(w, (int)p[3 * i]); a1 += __mul24(w, (int)p[3 * i + 1]); a2 += __mul24(w, (int)p[3 * i + 2]);
       }
     } else {  // [T,3,H,W]
-      const uint8_t* p = in + ((t * 3) * (size_t)H + y) * W + xmin;
+      const uint8_t* p = in + ((ts * 3) * (size_t)H + y) * W + xmin;
       const size_t cs = (size_t)H * W;
       for (int i = 0; i < xn; ++i) {
         const int w = k[i];
@@ -57,9 +109,10 @@ __global__ __launch_bounds__(256) void resample_h_kernel(const uint8_t* __restri
   }
 }
 
+template <int OT>
 __global__ __launch_bounds__(256) void resample_v_kernel(const uint8_t* __restrict__ tmp, int T, int nrows, int ow,
                                                          const int* __restrict__ coef, const int* __restrict__ bound,
-                                                         int oh, int ksize, int ylo, uint8_t* __restrict__ out) {
+                                                         int oh, int ksize, int ylo, void* __restrict__ out, pp_norm nm) {
   const size_t total = (size_t)T * 3 * oh * ow;
   for (size_t id = (size_t)blockIdx.x * 256 + threadIdx.x; id < total; id += (size_t)gridDim.x * 256) {
     const int x = (int)(id % ow);
@@ -70,7 +123,8 @@ __global__ __launch_bounds__(256) void resample_v_kernel(const uint8_t* __restri
     const uint8_t* p = tmp + (tc * nrows + ymin) * (size_t)ow + x;
     int a = 1 << 21;
     for (int i = 0; i < yn; ++i) a += __mul24(k[i], (int)p[(size_t)i * ow]);
-    out[id] = (uint8_t)clip8(a);
+    const int c = (int)(tc % 3);
+    pp_store1<OT>(out, id, clip8(a), c == 0 ? nm.a0 : (c == 1 ? nm.a1 : nm.a2), c == 0 ? nm.b0 : (c == 1 ? nm.b1 : nm.b2));
   }
 }
 
@@ -85,17 +139,19 @@ __global__ __launch_bounds__(256) void resample_v_kernel(const uint8_t* __restri
 // intermediate, coalesced along x).  Arithmetic (32-bit accumulators, 1 << 21 rounding, clip) is unchanged: bit-exact.
 #define PP_ROWS 64
 #define PP_XC 32
-template <int LAYOUT>
+template <int LAYOUT, bool IDX>
 __global__ __launch_bounds__(256) void resample_h_lds_kernel(const uint8_t* __restrict__ in, size_t in_bytes, int T, int H, int W,
                                                              const int* __restrict__ coef, const int* __restrict__ bound,
                                                              int ow, int ksize, int ylo, int nrows, int nrb, int nchunk,
-                                                             int pitch, uint8_t* __restrict__ tmp) {
+                                                             int pitch, uint8_t* __restrict__ tmp, const int64_t* __restrict__ index,
+                                                             int P, int* __restrict__ flag) {
   extern __shared__ uint32_t pp_lds[];   // LAYOUT 0 (THWC): [64][pitch]; LAYOUT 1 (TCHW): [3][64][pitch]   (pitch in bytes)
   constexpr int NP = LAYOUT == 0 ? 1 : 3, TS = LAYOUT == 0 ? 3 : 1;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int chunk = blockIdx.x % nchunk, rb = (blockIdx.x / nchunk) % nrb;
   const size_t t = blockIdx.x / ((size_t)nchunk * nrb);
+  const size_t ts = pp_src_frame<IDX>(index, t, P, flag);       // pool frame this output frame reads (workgroup-uniform)
   const int x0 = chunk * PP_XC, x1 = x0 + PP_XC < ow ? x0 + PP_XC : ow;
   const int xs = bound[2 * x0], xe = bound[2 * (x1 - 1)] + bound[2 * (x1 - 1) + 1];
   const int span = (xe - xs) * TS;
@@ -106,7 +162,7 @@ __global__ __launch_bounds__(256) void resample_h_lds_kernel(const uint8_t* __re
     int yy = yy0 + r;
     yy = yy < nrows ? yy : nrows - 1;
     const size_t y = (size_t)(ylo + yy);
-    const size_t off = LAYOUT == 0 ? ((t * H + y) * (size_t)W + xs) * 3 : ((t * 3 + pl) * (size_t)H + y) * W + xs;
+    const size_t off = LAYOUT == 0 ? ((ts * H + y) * (size_t)W + xs) * 3 : ((ts * 3 + pl) * (size_t)H + y) * W + xs;
     return reinterpret_cast<uintptr_t>(in) + off;
   };
   const uintptr_t in_end = reinterpret_cast<uintptr_t>(in) + in_bytes;
@@ -199,17 +255,19 @@ __global__ __launch_bounds__(256) void resample_h_lds_kernel(const uint8_t* __re
 // Same results bit for bit as the scalar kernels (tests/test_preprocess.py); ~5x fewer issued instructions per output.
 typedef int pp_v4i __attribute__((ext_vector_type(4)));
 #define PM_ROWS 32
-template <int LAYOUT, int NKB>
+template <int LAYOUT, int NKB, bool IDX>
 __global__ __launch_bounds__(256) void resample_h_mfma_kernel(const uint8_t* __restrict__ in, size_t in_bytes, int T, int H, int W,
                                                               const pp_v4i* __restrict__ atab, const int* __restrict__ bias,
                                                               const int* __restrict__ xs_tab, int nblk, int ow,
                                                               int ylo, int nrows, int nrb, int nchunk, int pitch,
-                                                              uint8_t* __restrict__ tmp) {
+                                                              uint8_t* __restrict__ tmp, const int64_t* __restrict__ index, int P,
+                                                              int* __restrict__ flag) {
   extern __shared__ uint32_t pm_lds[];   // [3 planes][32 rows][pitch bytes], pixels as signed bytes (p ^ 0x80)
   const int tid = threadIdx.x, lane = tid & 63, l15 = lane & 15, q4 = lane >> 4;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int chunk = blockIdx.x % nchunk, rb32 = (blockIdx.x / nchunk) % nrb;
   const size_t t = blockIdx.x / ((size_t)nchunk * nrb);
+  const size_t ts = pp_src_frame<IDX>(index, t, P, flag);       // pool frame this output frame reads (workgroup-uniform)
   constexpr int nkb = NKB;
   const int b0 = chunk * 4, b1 = b0 + 4 < nblk ? b0 + 4 : nblk;
   const int xs0 = xs_tab[b0];
@@ -224,8 +282,8 @@ __global__ __launch_bounds__(256) void resample_h_mfma_kernel(const uint8_t* __r
   int syy = yy0 + srow;
   syy = syy < nrows ? syy : nrows - 1;
   const size_t y = (size_t)(ylo + syy);
-  const uintptr_t rowbase0 = reinterpret_cast<uintptr_t>(in) + ((t * H + y) * (size_t)W + xs0) * 3;                // THWC
-  const uintptr_t rowbase1 = reinterpret_cast<uintptr_t>(in) + (t * 3) * frame_px + y * (size_t)W + xs0;           // TCHW, plane 0
+  const uintptr_t rowbase0 = reinterpret_cast<uintptr_t>(in) + ((ts * H + y) * (size_t)W + xs0) * 3;                // THWC
+  const uintptr_t rowbase1 = reinterpret_cast<uintptr_t>(in) + (ts * 3) * frame_px + y * (size_t)W + xs0;           // TCHW, plane 0
   for (int gi = tid & 7; gi < ngrp; gi += 8) {
     const int r = srow;
     uint32_t out3[3];                       // (columns past the row end read the next row's bytes: their taps are 0)
@@ -323,9 +381,10 @@ __global__ __launch_bounds__(256) void resample_h_mfma_kernel(const uint8_t* __r
 // up to 16 multiply-adds (PV_R = 8 was measured slower: 92 vs 75 us for 256 720p frames - too few workgroups per plane).  The taps of the rows are laid out in LDS against the wave's common input-row range, zero
 // outside a row's own range, so the loop has no branches; tap reads are LDS broadcasts (a wave's rows are uniform).
 #define PV_R 4
+template <int OT>
 __global__ __launch_bounds__(256) void resample_v4_kernel(const uint8_t* __restrict__ tmp, int T, int nrows, int ow,
                                                           const int* __restrict__ coef, const int* __restrict__ bound,
-                                                          int oh, int ksize, int ylo, int vspan, uint8_t* __restrict__ out) {
+                                                          int oh, int ksize, int ylo, int vspan, void* __restrict__ out, pp_norm nm) {
   extern __shared__ int pv_lds[];   // [4 waves][PV_R rows][vspan] taps against the wave's input-row range
   const int tid = threadIdx.x, lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -370,11 +429,13 @@ __global__ __launch_bounds__(256) void resample_v4_kernel(const uint8_t* __restr
       acc[rr][0] += __mul24(w, b0); acc[rr][1] += __mul24(w, b1); acc[rr][2] += __mul24(w, b2); acc[rr][3] += __mul24(w, b3);
     }
   }
+  const int c = (int)(tc % 3);                                    // workgroup-uniform: the constants are scalar selects
+  const float na = c == 0 ? nm.a0 : (c == 1 ? nm.a1 : nm.a2), nb = c == 0 ? nm.b0 : (c == 1 ? nm.b1 : nm.b2);
 #pragma unroll
   for (int rr = 0; rr < PV_R; ++rr)
     if (y0 + rr < oh)
-      *reinterpret_cast<uint32_t*>(out + (tc * oh + y0 + rr) * (size_t)ow + (size_t)x4 * 4) =
-          clip8(acc[rr][0]) | (clip8(acc[rr][1]) << 8) | (clip8(acc[rr][2]) << 16) | (clip8(acc[rr][3]) << 24);
+      pp_store4<OT>(out, (tc * oh + y0 + rr) * (size_t)ow + (size_t)x4 * 4, clip8(acc[rr][0]), clip8(acc[rr][1]), clip8(acc[rr][2]),
+                    clip8(acc[rr][3]), na, nb);
 }
 
 }  // namespace
@@ -384,90 +445,123 @@ extern "C" size_t tspo_preprocess_workspace_bytes(int T, int nrows, int out_w) {
   return tspo::align_up((size_t)T * 3 * nrows * out_w, 256);
 }
 
-static int preprocess_impl(const uint8_t* frames, int layout, int T, int H, int W, const int32_t* hcoef,
-                           const int32_t* hbound, int out_w, int hk, const int32_t* vcoef,
-                           const int32_t* vbound, int out_h, int vk, int ylo, int nrows, uint8_t* out,
-                           void* workspace, size_t workspace_bytes, tspo_stream_t stream, const int8_t* mfma_taps,
+// One body for the three entries.  `frames` is the pool [P,...]; output frame n < N reads pool frame index[n] (index == NULL: n,
+// and then P == N).  `what` names the entry in messages.
+static int preprocess_impl(const char* what, const uint8_t* frames, int layout, int P, int H, int W, const int64_t* index, int N,
+                           const int32_t* hcoef, const int32_t* hbound, int out_w, int hk, const int32_t* vcoef,
+                           const int32_t* vbound, int out_h, int vk, int ylo, int nrows, void* out, int out_dtype, pp_norm nm,
+                           int* flag, void* workspace, size_t workspace_bytes, tspo_stream_t stream, const int8_t* mfma_taps,
                            const int32_t* mfma_bias, const int32_t* mfma_xs, int mfma_nkb, int mfma_span) {
-  TSPO_REQUIRE(frames && hcoef && hbound && vcoef && vbound && out && workspace, "preprocess_frames: null pointer");
-  TSPO_REQUIRE(T >= 1 && H >= 1 && W >= 1 && out_w >= 1 && out_h >= 1 && hk >= 1 && vk >= 1, "preprocess_frames: bad dims");
-  TSPO_REQUIRE(layout == 0 || layout == 1, "preprocess_frames: layout must be 0 (THWC) or 1 (TCHW)");
-  TSPO_REQUIRE(ylo >= 0 && nrows >= 1 && ylo + nrows <= H, "preprocess_frames: row window [%d,%d) outside H=%d", ylo, ylo + nrows, H);
+  TSPO_REQUIRE(frames && hcoef && hbound && vcoef && vbound && out && workspace, "%s: null pointer", what);
+  TSPO_REQUIRE(P >= 1 && N >= 1 && H >= 1 && W >= 1 && out_w >= 1 && out_h >= 1 && hk >= 1 && vk >= 1, "%s: bad dims", what);
+  TSPO_REQUIRE(layout == 0 || layout == 1, "%s: layout must be 0 (THWC) or 1 (TCHW)", what);
+  TSPO_REQUIRE(ylo >= 0 && nrows >= 1 && ylo + nrows <= H, "%s: row window [%d,%d) outside H=%d", what, ylo, ylo + nrows, H);
+  const int T = N;
   const size_t need = tspo_preprocess_workspace_bytes(T, nrows, out_w);
   if (workspace_bytes < need)
-    return tspo::set_err(TSPO_EWORKSPACE, "preprocess_frames: workspace %zu < %zu", workspace_bytes, need);
+    return tspo::set_err(TSPO_EWORKSPACE, "%s: workspace %zu < %zu", what, workspace_bytes, need);
   hipStream_t st = (hipStream_t)stream;
   size_t n1 = (size_t)T * nrows * out_w, n2 = (size_t)T * 3 * out_h * out_w;
   unsigned g1 = (unsigned)((n1 + 255) / 256 > 65536 ? 65536 : (n1 + 255) / 256);
   unsigned g2 = (unsigned)((n2 + 255) / 256 > 65536 ? 65536 : (n2 + 255) / 256);
   // LDS-staged path: needs dword-aligned rows of the intermediate / output (out_w % 4 == 0) and the widest input span of
   // a 32-column chunk x 64 rows to fit the 64 KB of LDS a workgroup may use (scale factors up to ~14); the horizontal
-  // tables live on the device, so the span bound is computed from the geometry: 32 * scale + taps
-  const bool aligned = out_w % 4 == 0 && ((uintptr_t)workspace & 3) == 0 && ((uintptr_t)out & 3) == 0;
+  // tables live on the device, so the span bound is computed from the geometry: 32 * scale + taps.  Four adjacent output
+  // elements go out in one store: 4 bytes (uint8), 8 (bf16 / f16) or 16 (fp32) - the output must be aligned to that.
+  const size_t oalign = out_dtype == TSPO_U8 ? 4 : (out_dtype == TSPO_F32 ? 16 : 8);
+  const bool aligned = out_w % 4 == 0 && ((uintptr_t)workspace & 3) == 0 && ((uintptr_t)out & (oalign - 1)) == 0;
   // input rows that PV_R consecutive output rows can touch: the last row's taps start at most (PV_R - 1) * scale + 1 rows after
-  // the first's and add vk rows; vk = 2 * ceil(2 * scale) + 1 bounds the scale: scale <= (vk - 1) / 4
+  // the first's and add vk rows; vk = 2 * ceil(2 * max(scale, 1)) + 1 bounds the scale: scale <= (vk - 1) / 4
+  // (vspan, span_px and the matrix pass's LDS bytes are restated in tspo_amd/preprocess.py:kernel_lds_sizing, which the tests hold
+  // real tap tables against - keep the two in step)
   const int vspan = vk > 1 ? ((PV_R - 1) * (vk - 1) + 3) / 4 + vk + 2 : PV_R;
+  const size_t in_bytes = (size_t)P * H * W * 3;
+  const size_t g4 = (size_t)T * 3 * ((out_h + 4 * PV_R - 1) / (4 * PV_R)) * ((out_w / 4 + 63) / 64);
+#define PV4_LAUNCH(OT)                                                                                                         \
+  hipLaunchKernelGGL(resample_v4_kernel<OT>, dim3((unsigned)g4), dim3(256), (size_t)4 * PV_R * vspan * 4, st,                  \
+                     (const uint8_t*)workspace, T, nrows, out_w, vcoef, vbound, out_h, vk, ylo, vspan, out, nm)
+#define PV4_DISPATCH()                                                                                                         \
+  do {                                                                                                                         \
+    if (out_dtype == TSPO_U8) PV4_LAUNCH(TSPO_U8); else if (out_dtype == TSPO_F32) PV4_LAUNCH(TSPO_F32);                       \
+    else if (out_dtype == TSPO_BF16) PV4_LAUNCH(TSPO_BF16); else PV4_LAUNCH(TSPO_F16);                                         \
+  } while (0)
   // matrix-pipe horizontal pass: the caller supplies the digit-split tap matrices (tspo_amd/preprocess.py builds them with
   // the tap tables); needs 16-column blocks, at most 4 K blocks of 64 input columns per block and planes that fit in LDS
   if (mfma_taps && aligned && out_w % 16 == 0 && mfma_nkb >= 1 && mfma_nkb <= 4 && hk > 1) {
-    TSPO_REQUIRE(mfma_bias && mfma_xs && mfma_span >= 1, "preprocess_frames_ex: incomplete matrix-pass tables");
+    TSPO_REQUIRE(mfma_bias && mfma_xs && mfma_span >= 1, "%s: incomplete matrix-pass tables", what);
     int mp = ((mfma_span + 16 + 3) / 4) * 4;
     if (((mp >> 2) & 1) == 0) mp += 4;
     const size_t mlds = (size_t)3 * PM_ROWS * mp;
     if (mlds <= 64 * 1024) {
       const int nblk = out_w / 16, nchunk = (nblk + 3) / 4, nrb = (nrows + PM_ROWS - 1) / PM_ROWS;
-      const size_t in_bytes = (size_t)T * H * W * 3;
       const unsigned grid = (unsigned)((size_t)T * nrb * nchunk);
-#define PM_LAUNCH(L, K)                                                                                                   \
-  hipLaunchKernelGGL((resample_h_mfma_kernel<L, K>), dim3(grid), dim3(256), mlds, st, frames, in_bytes, T, H, W,               \
-                     (const pp_v4i*)mfma_taps, mfma_bias, mfma_xs, nblk, out_w, ylo, nrows, nrb, nchunk, mp, (uint8_t*)workspace)
+#define PM_LAUNCH(L, K, I)                                                                                                \
+  hipLaunchKernelGGL((resample_h_mfma_kernel<L, K, I>), dim3(grid), dim3(256), mlds, st, frames, in_bytes, T, H, W,            \
+                     (const pp_v4i*)mfma_taps, mfma_bias, mfma_xs, nblk, out_w, ylo, nrows, nrb, nchunk, mp, (uint8_t*)workspace, \
+                     index, P, flag)
+#define PM_LAUNCH_K(L, I)                                                                                                 \
+  do {                                                                                                                    \
+    if (mfma_nkb == 1) PM_LAUNCH(L, 1, I); else if (mfma_nkb == 2) PM_LAUNCH(L, 2, I);                                    \
+    else if (mfma_nkb == 3) PM_LAUNCH(L, 3, I); else PM_LAUNCH(L, 4, I);                                                  \
+  } while (0)
       if (layout == 0) {
-        if (mfma_nkb == 1) PM_LAUNCH(0, 1); else if (mfma_nkb == 2) PM_LAUNCH(0, 2); else if (mfma_nkb == 3) PM_LAUNCH(0, 3); else PM_LAUNCH(0, 4);
+        if (index) PM_LAUNCH_K(0, true); else PM_LAUNCH_K(0, false);
       } else {
-        if (mfma_nkb == 1) PM_LAUNCH(1, 1); else if (mfma_nkb == 2) PM_LAUNCH(1, 2); else if (mfma_nkb == 3) PM_LAUNCH(1, 3); else PM_LAUNCH(1, 4);
+        if (index) PM_LAUNCH_K(1, true); else PM_LAUNCH_K(1, false);
       }
+#undef PM_LAUNCH_K
 #undef PM_LAUNCH
-      const size_t g4 = (size_t)T * 3 * ((out_h + 4 * PV_R - 1) / (4 * PV_R)) * ((out_w / 4 + 63) / 64);
-      hipLaunchKernelGGL(resample_v4_kernel, dim3((unsigned)g4), dim3(256), (size_t)4 * PV_R * vspan * 4, st, (const uint8_t*)workspace, T,
-                         nrows, out_w, vcoef, vbound, out_h, vk, ylo, vspan, out);
-      return tspo::check_launch("preprocess_frames");
+      PV4_DISPATCH();
+      return tspo::check_launch(what);
     }
   }
   const int ts = layout == 0 ? 3 : 1, planes = layout == 0 ? 1 : 3;
   // span of a chunk in pixels: xmin advances by at most scale per column (+1 for the truncation) and the last column adds
-  // its taps; ksize = 2 * ceil(2 * scale) + 1 bounds the scale from above: scale <= (hk - 1) / 4
+  // its taps; ksize = 2 * ceil(2 * max(scale, 1)) + 1 bounds the scale from above: scale <= (hk - 1) / 4
   const int span_px = (31 * (hk - 1) + 3) / 4 + hk + 2;
   int pitch = ((span_px * ts + 8 + 3) / 4 + 1) * 4;
   if (((pitch >> 2) & 1) == 0) pitch += 4;                                      // odd number of dwords: conflict-free rows
   const size_t lds_bytes = (size_t)planes * PP_ROWS * pitch + (size_t)PP_XC * (hk + 2) * 4;
   if (aligned && lds_bytes <= 64 * 1024 && hk > 1) {
     const int nrb = (nrows + PP_ROWS - 1) / PP_ROWS, nchunk = (out_w + PP_XC - 1) / PP_XC;
-    const size_t in_bytes = (size_t)T * H * W * 3;
     const unsigned grid = (unsigned)((size_t)T * nrb * nchunk);
-    if (layout == 0)
-      hipLaunchKernelGGL(resample_h_lds_kernel<0>, dim3(grid), dim3(256), lds_bytes, st, frames, in_bytes, T, H, W, hcoef, hbound,
-                         out_w, hk, ylo, nrows, nrb, nchunk, pitch, (uint8_t*)workspace);
-    else
-      hipLaunchKernelGGL(resample_h_lds_kernel<1>, dim3(grid), dim3(256), lds_bytes, st, frames, in_bytes, T, H, W, hcoef, hbound,
-                         out_w, hk, ylo, nrows, nrb, nchunk, pitch, (uint8_t*)workspace);
-    const size_t g4 = (size_t)T * 3 * ((out_h + 4 * PV_R - 1) / (4 * PV_R)) * ((out_w / 4 + 63) / 64);
-    hipLaunchKernelGGL(resample_v4_kernel, dim3((unsigned)g4), dim3(256), (size_t)4 * PV_R * vspan * 4, st, (const uint8_t*)workspace, T,
-                       nrows, out_w, vcoef, vbound, out_h, vk, ylo, vspan, out);
-    return tspo::check_launch("preprocess_frames");
+#define PL_LAUNCH(L, I)                                                                                                       \
+  hipLaunchKernelGGL((resample_h_lds_kernel<L, I>), dim3(grid), dim3(256), lds_bytes, st, frames, in_bytes, T, H, W, hcoef, hbound, \
+                     out_w, hk, ylo, nrows, nrb, nchunk, pitch, (uint8_t*)workspace, index, P, flag)
+    if (layout == 0) {
+      if (index) PL_LAUNCH(0, true); else PL_LAUNCH(0, false);
+    } else {
+      if (index) PL_LAUNCH(1, true); else PL_LAUNCH(1, false);
+    }
+#undef PL_LAUNCH
+    PV4_DISPATCH();
+    return tspo::check_launch(what);
   }
-  hipLaunchKernelGGL(resample_h_kernel, dim3(g1), dim3(256), 0, st, frames, layout, T, H, W, hcoef, hbound, out_w, hk, ylo,
-                     nrows, (uint8_t*)workspace);
-  hipLaunchKernelGGL(resample_v_kernel, dim3(g2), dim3(256), 0, st, (const uint8_t*)workspace, T, nrows, out_w, vcoef,
-                     vbound, out_h, vk, ylo, out);
-  return tspo::check_launch("preprocess_frames");
+#undef PV4_DISPATCH
+#undef PV4_LAUNCH
+#define PH_LAUNCH(I)                                                                                                          \
+  hipLaunchKernelGGL(resample_h_kernel<I>, dim3(g1), dim3(256), 0, st, frames, layout, T, H, W, hcoef, hbound, out_w, hk, ylo, \
+                     nrows, (uint8_t*)workspace, index, P, flag)
+  if (index) PH_LAUNCH(true); else PH_LAUNCH(false);
+#undef PH_LAUNCH
+#define PV_LAUNCH(OT)                                                                                                         \
+  hipLaunchKernelGGL(resample_v_kernel<OT>, dim3(g2), dim3(256), 0, st, (const uint8_t*)workspace, T, nrows, out_w, vcoef,     \
+                     vbound, out_h, vk, ylo, out, nm)
+  if (out_dtype == TSPO_U8) PV_LAUNCH(TSPO_U8); else if (out_dtype == TSPO_F32) PV_LAUNCH(TSPO_F32);
+  else if (out_dtype == TSPO_BF16) PV_LAUNCH(TSPO_BF16); else PV_LAUNCH(TSPO_F16);
+#undef PV_LAUNCH
+  return tspo::check_launch(what);
 }
+
+static const pp_norm PP_NO_NORM = {1.f, 1.f, 1.f, 0.f, 0.f, 0.f};
 
 extern "C" int tspo_preprocess_frames(const uint8_t* frames, int layout, int T, int H, int W, const int32_t* hcoef,
                                       const int32_t* hbound, int out_w, int hk, const int32_t* vcoef,
                                       const int32_t* vbound, int out_h, int vk, int ylo, int nrows, uint8_t* out,
                                       void* workspace, size_t workspace_bytes, tspo_stream_t stream) {
-  return preprocess_impl(frames, layout, T, H, W, hcoef, hbound, out_w, hk, vcoef, vbound, out_h, vk, ylo, nrows, out, workspace,
-                         workspace_bytes, stream, nullptr, nullptr, nullptr, 0, 0);
+  return preprocess_impl("preprocess_frames", frames, layout, T, H, W, nullptr, T, hcoef, hbound, out_w, hk, vcoef, vbound, out_h, vk,
+                         ylo, nrows, out, TSPO_U8, PP_NO_NORM, nullptr, workspace, workspace_bytes, stream, nullptr, nullptr, nullptr,
+                         0, 0);
 }
 
 extern "C" int tspo_preprocess_frames_ex(const uint8_t* frames, int layout, int T, int H, int W, const int32_t* hcoef,
@@ -476,6 +570,34 @@ extern "C" int tspo_preprocess_frames_ex(const uint8_t* frames, int layout, int 
                                          void* workspace, size_t workspace_bytes, tspo_stream_t stream,
                                          const int8_t* mfma_taps, const int32_t* mfma_bias, const int32_t* mfma_xs, int mfma_nkb,
                                          int mfma_span) {
-  return preprocess_impl(frames, layout, T, H, W, hcoef, hbound, out_w, hk, vcoef, vbound, out_h, vk, ylo, nrows, out, workspace,
-                         workspace_bytes, stream, mfma_taps, mfma_bias, mfma_xs, mfma_nkb, mfma_span);
+  return preprocess_impl("preprocess_frames", frames, layout, T, H, W, nullptr, T, hcoef, hbound, out_w, hk, vcoef, vbound, out_h, vk,
+                         ylo, nrows, out, TSPO_U8, PP_NO_NORM, nullptr, workspace, workspace_bytes, stream, mfma_taps, mfma_bias,
+                         mfma_xs, mfma_nkb, mfma_span);
+}
+
+extern "C" int tspo_preprocess_select(const uint8_t* pool, int layout, int P, int H, int W, const int64_t* index, int N,
+                                      const int32_t* hcoef, const int32_t* hbound, int out_w, int hk, const int32_t* vcoef,
+                                      const int32_t* vbound, int out_h, int vk, int ylo, int nrows, void* out, int out_dtype,
+                                      double rescale, const double* mean3, const double* std3, int32_t* oob_flag, void* workspace,
+                                      size_t workspace_bytes, tspo_stream_t stream, const int8_t* mfma_taps,
+                                      const int32_t* mfma_bias, const int32_t* mfma_xs, int mfma_nkb, int mfma_span) {
+  TSPO_REQUIRE(pool, "preprocess_select: null pointer (pool)");
+  TSPO_REQUIRE(P >= 1 && N >= 1, "preprocess_select: bad dims (P=%d, N=%d)", P, N);
+  TSPO_REQUIRE(index || N == P, "preprocess_select: index == NULL means frames 0..P-1, so N must equal P (N=%d, P=%d)", N, P);
+  TSPO_REQUIRE(out_dtype == TSPO_U8 || out_dtype == TSPO_F32 || out_dtype == TSPO_BF16 || out_dtype == TSPO_F16,
+               "preprocess_select: unknown out_dtype %d", out_dtype);
+  pp_norm nm = PP_NO_NORM;
+  if (out_dtype != TSPO_U8) {
+    TSPO_REQUIRE(mean3 && std3, "preprocess_select: null pointer (mean / std of a float output)");
+    TSPO_REQUIRE(std3[0] != 0.0 && std3[1] != 0.0 && std3[2] != 0.0 && rescale == rescale && std3[0] == std3[0] &&
+                     std3[1] == std3[1] && std3[2] == std3[2],
+                 "preprocess_select: std == 0 (or NaN) - the normalisation divides by it");
+    // (u * rescale - mean) / std = u * a + b; the quotients are taken in double and rounded once to fp32
+    nm.a0 = (float)(rescale / std3[0]); nm.b0 = (float)(-mean3[0] / std3[0]);
+    nm.a1 = (float)(rescale / std3[1]); nm.b1 = (float)(-mean3[1] / std3[1]);
+    nm.a2 = (float)(rescale / std3[2]); nm.b2 = (float)(-mean3[2] / std3[2]);
+  }
+  return preprocess_impl("preprocess_select", pool, layout, P, H, W, index, N, hcoef, hbound, out_w, hk, vcoef, vbound, out_h, vk, ylo,
+                         nrows, out, out_dtype, nm, (int*)oob_flag, workspace, workspace_bytes, stream, mfma_taps, mfma_bias, mfma_xs,
+                         mfma_nkb, mfma_span);
 }

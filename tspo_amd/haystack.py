@@ -89,6 +89,60 @@ def build_specific_sample(video, distractor_clips: Sequence, repeat_times: Optio
     return shuffle_clips(true_videos, list(distractor_clips), rng=rng)
 
 
+# ---- the same three steps as index plans -----------------------------------------------------------------------------------
+# The haystack is a gather of the pool [video frames || distractor clip 0 || ... || distractor clip n-1]: the twins below consume
+# the SAME random stream draw for draw and return the gather indices instead of frames, so `pool[plan]` is element for element
+# what `build_specific_sample` returns and the haystack never has to exist at source resolution (the front end of the encoder
+# reads `pool` through `plan`, the reward model's frames are `pool` through `plan[idx]`: preprocess.select_frames).
+
+def repeat_plan(n_video_frames: int, repeat_times: int = 4, sample_len: int = 50, rng=None) -> List[np.ndarray]:
+    """`repeat_videos` on frame numbers: `repeat_times` int64 index arrays into the video."""
+    r = _rng(rng)
+    if n_video_frames <= sample_len:
+        return [np.arange(n_video_frames, dtype=np.int64) for _ in range(repeat_times)]
+    return [np.sort(r.choice(n_video_frames, size=sample_len, replace=False)).astype(np.int64) for _ in range(repeat_times)]
+
+
+def shuffle_plan(true_groups: Sequence[np.ndarray], wrong_groups: Sequence[np.ndarray], rng=None):
+    """`shuffle_clips` on index arrays -> (plan int64 [G*len], shuffle_mask bool [G*len])."""
+    r = _rng(rng)
+    len_group = len(true_groups[0])
+    total_groups = [1] * len(true_groups) + [0] * len(wrong_groups)
+    order = r.permutation(total_groups)
+    parts, mask = [], np.zeros(len(total_groups) * len_group, dtype=bool)
+    count_ori = count_wrong = 0
+    for i, flag in enumerate(order):
+        if flag == 1:
+            parts.append(true_groups[count_ori])
+            mask[i * len_group:(i + 1) * len_group] = True
+            count_ori += 1
+        else:
+            parts.append(wrong_groups[count_wrong])
+            count_wrong += 1
+    return torch.from_numpy(np.concatenate(parts).astype(np.int64)), torch.tensor(mask)
+
+
+def build_specific_plan(n_video_frames: int, n_distractor_clips: int = 12, repeat_times: Optional[int] = None,
+                        sample_len: int = 50, rng=None, py_random: Optional[_random.Random] = None):
+    """`build_specific_sample` as an index plan into the pool [video (n_video_frames) || n_distractor_clips clips of
+    min(n_video_frames, sample_len) frames each]: -> (plan int64 [T], shuffle_mask bool [T]), both on the CPU.  Under the
+    same `rng` / `py_random` state, `pool[plan]` equals the frames `build_specific_sample` returns, the masks are equal and
+    the generators end in the same state."""
+    if repeat_times is None:
+        repeat_times = (py_random or _random).randint(1, 4)
+    true_groups = repeat_plan(n_video_frames, repeat_times=repeat_times, sample_len=sample_len, rng=rng)
+    glen = len(true_groups[0])
+    wrong = [n_video_frames + c * glen + np.arange(glen, dtype=np.int64) for c in range(n_distractor_clips)]
+    return shuffle_plan(true_groups, wrong, rng=rng)
+
+
+def haystack_pool(video, distractor_clips: Sequence):
+    """The pool `build_specific_plan` indexes: the video followed by the distractor clips (numpy or torch, as given)."""
+    if isinstance(video, torch.Tensor):
+        return torch.cat([video] + [c.to(video.device) for c in distractor_clips], dim=0)
+    return np.concatenate([video] + list(distractor_clips))
+
+
 def general_sample_mask(video) -> torch.Tensor:
     """tspo_trainer.py:482: "general" items keep the video as it is; every frame counts as relevant."""
     return torch.ones(len(video)).bool()

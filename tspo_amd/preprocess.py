@@ -9,7 +9,8 @@ from __future__ import annotations
 import ctypes as C
 import functools
 import math
-from typing import Tuple
+from dataclasses import dataclass
+from typing import Optional, Tuple
 
 import numpy as np
 import torch
@@ -118,39 +119,216 @@ def mfma_h_tables(hk: np.ndarray, hb: np.ndarray):
     return frag, bias.astype(np.int32), xs.astype(np.int32), nkb, span
 
 
-_dev_tables = {}
+CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)
+CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
 
 
-def preprocess_frames(frames: torch.Tensor, size: int = 224) -> torch.Tensor:
-    """uint8 CUDA frames [T,H,W,3] or [T,3,H,W] -> uint8 [T,3,size,size] (resize + centre crop, Pillow-exact)."""
-    from . import _lib, ops
-    ops._need_gpu(frames)
+@dataclass(frozen=True)
+class PreprocessSpec:
+    """What an image processor does to a uint8 RGB frame, in the terms `tspo_preprocess_select` takes.  Resize rule: either
+    `shortest_edge` (shortest edge -> that many pixels, long side int()-truncated, then a centre crop `crop` = (h, w): the
+    CLIPImageProcessor rule) or `size` = exact (h, w) without crop (the reference's SigLipImageProcessor,
+    llava/model/multimodal_encoder/siglip_encoder.py:34-61); PIL antialiased bicubic either way.  Float outputs are
+    (u * rescale - mean[c]) / std[c]; `out_dtype` torch.uint8 stops at the Pillow-exact bytes u."""
+    shortest_edge: Optional[int] = None
+    crop: Optional[Tuple[int, int]] = None
+    size: Optional[Tuple[int, int]] = None
+    rescale: float = 1 / 255
+    mean: Tuple[float, float, float] = CLIP_MEAN
+    std: Tuple[float, float, float] = CLIP_STD
+    out_dtype: torch.dtype = torch.float32
+
+    def __post_init__(self):
+        if (self.shortest_edge is None) == (self.size is None):
+            raise ValueError("PreprocessSpec: give either shortest_edge (+ crop) or an exact size")
+        if self.shortest_edge is not None and self.crop is None:
+            object.__setattr__(self, "crop", (int(self.shortest_edge), int(self.shortest_edge)))
+        if self.size is not None and self.crop is not None:
+            raise ValueError("PreprocessSpec: an exact size takes no crop")
+        if self.out_dtype not in _OUT_DTYPES:
+            raise ValueError(f"PreprocessSpec: out_dtype must be one of {sorted(map(str, _OUT_DTYPES))}")
+        if len(self.mean) != 3 or len(self.std) != 3:
+            raise ValueError("PreprocessSpec: mean and std have one entry per RGB channel")
+        object.__setattr__(self, "mean", tuple(float(v) for v in self.mean))
+        object.__setattr__(self, "std", tuple(float(v) for v in self.std))
+
+    @property
+    def geometry(self):
+        """The part the tap tables depend on."""
+        return (self.shortest_edge, self.crop, self.size)
+
+    @property
+    def out_hw(self) -> Tuple[int, int]:
+        return tuple(self.size) if self.size is not None else tuple(self.crop)
+
+    def with_dtype(self, out_dtype: torch.dtype) -> "PreprocessSpec":
+        return PreprocessSpec(self.shortest_edge, self.crop, self.size, self.rescale, self.mean, self.std, out_dtype)
+
+    @classmethod
+    def clip_default(cls, size: int = 224, out_dtype: torch.dtype = torch.float32) -> "PreprocessSpec":
+        """openai/clip-vit-large-patch14's processor: what `processor_is_default_clip` recognises."""
+        return cls(shortest_edge=size, crop=(size, size), out_dtype=out_dtype)
+
+    @classmethod
+    def from_image_processor(cls, ip, out_dtype: torch.dtype = torch.float32) -> Optional["PreprocessSpec"]:
+        """The spec of an HF CLIPImageProcessor-shaped object or of the reference's SigLipImageProcessor shape
+        (`size=(384, 384)`, `resample` bicubic, `image_mean`, `image_std`, `rescale_factor`), or None for anything the
+        kernel does not reproduce exactly (another resampling filter, padding, a disabled stage, Qwen's smart_resize, a
+        size rule it does not know): the caller then keeps its own processor - no silent approximation.  Frames handed to
+        `select_frames` are 3-channel uint8, so `do_convert_rgb` is a no-op on them."""
+        g = lambda n, d=None: getattr(ip, n, d)
+        if ip is None or not all(hasattr(ip, n) for n in ("resample", "size", "image_mean", "image_std", "rescale_factor")):
+            return None
+        # anything that makes the processor do MORE than resize -> (crop) -> rescale -> normalize on one RGB image
+        for extra in _UNSUPPORTED_PROCESSOR_ATTRS:
+            if g(extra) not in (None, False):
+                return None
+        try:
+            resample = int(g("resample"))
+        except (TypeError, ValueError):
+            return None
+        if resample != 3:                                                       # PIL.Image.BICUBIC
+            return None
+        for stage in ("do_resize", "do_rescale", "do_normalize"):              # absent (SigLIP shape): the stage always runs
+            if g(stage, True) is not True:
+                return None
+        mean, std, rescale = g("image_mean"), g("image_std"), g("rescale_factor")
+        if (not isinstance(mean, (list, tuple)) or not isinstance(std, (list, tuple)) or not isinstance(rescale, (int, float))
+                or len(mean) != 3 or len(std) != 3 or any(float(v) == 0 for v in std)):
+            return None
+        common = dict(rescale=float(rescale), mean=tuple(float(v) for v in mean), std=tuple(float(v) for v in std),
+                      out_dtype=out_dtype)
+        size = g("size")
+        if isinstance(size, (tuple, list)):                                    # SigLipImageProcessor: exact (h, w), never crops
+            if len(size) != 2 or hasattr(ip, "do_center_crop"):
+                return None
+            return cls(size=(int(size[0]), int(size[1])), **common)
+        try:
+            size = {k: v for k, v in dict(size).items() if v is not None}
+        except (TypeError, ValueError):
+            return None
+        if set(size) == {"shortest_edge"}:
+            cs = {k: v for k, v in dict(g("crop_size") or {}).items() if v is not None}
+            if g("do_center_crop") is not True or set(cs) != {"height", "width"}:
+                return None
+            se, ch, cw = int(size["shortest_edge"]), int(cs["height"]), int(cs["width"])
+            if ch > se or cw > se:                                             # a crop larger than the image pads
+                return None
+            return cls(shortest_edge=se, crop=(ch, cw), **common)
+        if set(size) == {"height", "width"} and not g("do_center_crop", False):
+            return cls(size=(int(size["height"]), int(size["width"])), **common)
+        return None
+
+
+# attributes of HF-style processors that split, tile, pad, flip or re-grid the image: a processor that sets one of them does
+# something `tspo_preprocess_select` does not, so no spec is returned for it
+_UNSUPPORTED_PROCESSOR_ATTRS = ("do_pad", "min_pixels", "max_pixels", "patch_size", "merge_size", "temporal_patch_size",
+                                "do_image_splitting", "image_grid_pinpoints", "do_flip_channel_order", "do_convert_grayscale",
+                                "do_thumbnail", "do_align_long_axis", "do_crop_margin", "do_pan_and_scan", "crop_to_patches",
+                                "max_image_size", "size_divisor")
+
+
+def kernel_lds_sizing(hk: int, vk: int, mfma_span: int = 0):
+    """The three LDS sizing numbers of preprocess.hip (preprocess_impl), restated on the host so that tests can hold real tap
+    tables against them - KEEP IN STEP with the kernel file: (vspan: input rows that PV_R = 4 consecutive output rows may
+    touch; span_px: input pixels a 32-column chunk of the LDS-staged horizontal pass may touch; mfma_lds_bytes: LDS of the
+    matrix-pass workgroup for a chunk span of `mfma_span` pixels, which must be <= 64 KB for that pass to be taken)."""
+    vspan = ((4 - 1) * (vk - 1) + 3) // 4 + vk + 2 if vk > 1 else 4
+    span_px = (31 * (hk - 1) + 3) // 4 + hk + 2
+    mp = ((mfma_span + 16 + 3) // 4) * 4
+    if ((mp >> 2) & 1) == 0:
+        mp += 4
+    return vspan, span_px, 3 * 32 * mp
+
+
+_OUT_DTYPES = {torch.uint8: 3, torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}       # -> TSPO_U8 / F32 / BF16 / F16
+
+
+def spec_resize_geometry(H: int, W: int, spec: PreprocessSpec):
+    """-> (new_h, new_w, top, left, out_h, out_w): resize to new_h x new_w, output window of out_h x out_w at (top, left)."""
+    if spec.size is not None:
+        return spec.size[0], spec.size[1], 0, 0, spec.size[0], spec.size[1]
+    new_h, new_w, _, _ = clip_resize_geometry(H, W, spec.shortest_edge)
+    oh, ow = spec.crop
+    if oh > new_h or ow > new_w:
+        raise ValueError(f"crop {spec.crop} larger than the resized image {new_h}x{new_w}: padding is not reproduced")
+    return new_h, new_w, (new_h - oh) // 2, (new_w - ow) // 2, oh, ow
+
+
+@functools.lru_cache(maxsize=32)
+def _spec_tables(H: int, W: int, geometry):
+    spec = PreprocessSpec(shortest_edge=geometry[0], crop=geometry[1], size=geometry[2])
+    new_h, new_w, top, left, oh, ow = spec_resize_geometry(H, W, spec)
+    hk, hb = pil_bicubic_tables(W, new_w, left, ow)
+    vk, vb = pil_bicubic_tables(H, new_h, top, oh)
+    ylo = int(vb[:, 0].min())
+    yhi = int((vb[:, 0] + vb[:, 1]).max())
+    return hk, hb, vk, vb, ylo, yhi - ylo
+
+
+_dev_tables = {}          # (H, W, spec geometry, device) -> device tables
+
+
+def _frame_layout(frames: torch.Tensor, what: str):
     if frames.dtype != torch.uint8 or frames.ndim != 4:
-        raise TypeError("preprocess_frames expects a uint8 tensor [T,H,W,3] or [T,3,H,W]")
+        raise TypeError(f"{what} expects a uint8 tensor [T,H,W,3] or [T,3,H,W]")
     layout = 0 if frames.shape[-1] == 3 else 1
     if layout == 1 and frames.shape[1] != 3:
         raise ValueError(f"cannot infer the channel axis of {tuple(frames.shape)}")
-    fr = frames.contiguous()
-    T = fr.shape[0]
-    H, W = (fr.shape[1], fr.shape[2]) if layout == 0 else (fr.shape[2], fr.shape[3])
-    key = (H, W, size, fr.device)
+    H, W = (frames.shape[1], frames.shape[2]) if layout == 0 else (frames.shape[2], frames.shape[3])
+    return layout, int(H), int(W)
+
+
+def select_frames(pool: torch.Tensor, index: Optional[torch.Tensor], spec: PreprocessSpec,
+                  oob_flag: Optional[torch.Tensor] = None, what: str = "select_frames") -> torch.Tensor:
+    """Frames `index` of the uint8 pool [P,H,W,3] / [P,3,H,W] through the image processor `spec` describes, in one HIP call
+    (`tspo_preprocess_select`): -> [*index.shape, 3, h, w] of spec.out_dtype.  `index`: int64 on the pool's device, any shape
+    (e.g. the [B,G,k] of a rollout), repeats and any order allowed, read ON THE DEVICE - nothing is copied to the host and
+    nothing synchronises; None = every frame in order.  A value outside [0, P) is clamped to the nearest frame; pass
+    `oob_flag` (int32 [1] on the device, zeroed) to learn that it happened.  Replaces tspo_trainer.py:516,524."""
+    from . import _lib, ops
+    ops._need_gpu(pool)
+    layout, H, W = _frame_layout(pool, what)
+    fr = pool.contiguous()
+    P_ = int(fr.shape[0])
+    if index is None:
+        lead, N, ix = (P_,), P_, None
+    else:
+        ops._need_gpu(index)
+        if index.dtype != torch.int64 or index.device != fr.device:
+            raise TypeError("select_frames: index must be an int64 tensor on the pool's device")
+        lead, ix = tuple(index.shape), index.reshape(-1).contiguous()
+        N = int(ix.numel())
+    if P_ < 1 or N < 1:
+        raise ValueError(f"select_frames: empty pool or index (P={P_}, N={N})")
+    key = (H, W, spec.geometry, fr.device)
     if key not in _dev_tables:
-        hk, hb, vk, vb, ylo, nrows = _tables(H, W, size)
+        hk, hb, vk, vb, ylo, nrows = _spec_tables(H, W, spec.geometry)
         mf = mfma_h_tables(hk, hb)
         dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(fr.device)
         _dev_tables[key] = tuple(dev(a) for a in (hk, hb, vk, vb)) + (ylo, nrows) + \
             ((dev(mf[0]), dev(mf[1]), dev(mf[2]), mf[3], mf[4]) if mf is not None else (None, None, None, 0, 0))
     hk, hb, vk, vb, ylo, nrows, mtaps, mbias, mxs, mnkb, mspan = _dev_tables[key]
-    out = torch.empty((T, 3, size, size), dtype=torch.uint8, device=fr.device)
-    nws = _lib.lib().tspo_preprocess_workspace_bytes(T, nrows, size)
+    oh, ow = spec.out_hw
+    out = torch.empty((N, 3, oh, ow), dtype=spec.out_dtype, device=fr.device)
+    nws = _lib.lib().tspo_preprocess_workspace_bytes(N, nrows, ow)
     ws = torch.empty((nws,), dtype=torch.uint8, device=fr.device)
+    if oob_flag is not None and (oob_flag.dtype != torch.int32 or oob_flag.device != fr.device or oob_flag.numel() < 1):
+        raise TypeError("select_frames: oob_flag must be an int32 tensor on the pool's device")
     P = lambda t_: None if t_ is None else C.c_void_p(t_.data_ptr())
-    _lib.check(_lib.lib().tspo_preprocess_frames_ex(
-        C.c_void_p(fr.data_ptr()), layout, T, H, W, C.c_void_p(hk.data_ptr()), C.c_void_p(hb.data_ptr()), size, hk.shape[1],
-        C.c_void_p(vk.data_ptr()), C.c_void_p(vb.data_ptr()), size, vk.shape[1], ylo, nrows, C.c_void_p(out.data_ptr()),
-        C.c_void_p(ws.data_ptr()), ws.numel(), torch.cuda.current_stream().cuda_stream,
-        P(mtaps) if USE_MATRIX_PASS else None, P(mbias), P(mxs), int(mnkb), int(mspan)), "tspo_preprocess_frames_ex")
-    return out
+    mean3, std3 = (C.c_double * 3)(*spec.mean), (C.c_double * 3)(*spec.std)
+    _lib.check(_lib.lib().tspo_preprocess_select(
+        C.c_void_p(fr.data_ptr()), layout, P_, H, W, P(ix), N, C.c_void_p(hk.data_ptr()), C.c_void_p(hb.data_ptr()), ow, hk.shape[1],
+        C.c_void_p(vk.data_ptr()), C.c_void_p(vb.data_ptr()), oh, vk.shape[1], ylo, nrows, C.c_void_p(out.data_ptr()),
+        _OUT_DTYPES[spec.out_dtype], float(spec.rescale), mean3, std3, P(oob_flag), C.c_void_p(ws.data_ptr()), ws.numel(),
+        torch.cuda.current_stream().cuda_stream, P(mtaps) if USE_MATRIX_PASS else None, P(mbias), P(mxs), int(mnkb), int(mspan)),
+        "tspo_preprocess_select")
+    return out.view(*lead, 3, oh, ow)
+
+
+def preprocess_frames(frames: torch.Tensor, size: int = 224) -> torch.Tensor:
+    """uint8 CUDA frames [T,H,W,3] or [T,3,H,W] -> uint8 [T,3,size,size] (resize + centre crop, Pillow-exact)."""
+    return select_frames(frames, None, PreprocessSpec.clip_default(size, torch.uint8), what="preprocess_frames")
 
 
 def processor_is_default_clip(image_processor, size: int = 224) -> bool:

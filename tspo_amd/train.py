@@ -31,8 +31,9 @@ import json
 import os
 import time
 from dataclasses import asdict, dataclass
-from typing import Callable, Dict, Iterator, List, Optional
+from typing import Callable, Dict, Iterator, List, Optional, Sequence
 
+import numpy as np
 import torch
 
 from . import dist as tdist
@@ -67,10 +68,15 @@ class Batch:
     """One micro-batch of prompts on this rank: features [B,T,D], text [B,1,D], clip [B,T], mask [B,T] bool, type, and `meta`:
     ALWAYS a list of length B - entry b describes prompt b (e.g. {"path": ...} of its feature cache; None when the data set has
     nothing to say).  The same convention holds for a single micro-batch and for the stacked batch of a coalesced accumulation
-    window (round 6, ADVICE r5: a reward plug-in that reads `batch.meta[b]` sees the same thing on stacked and unstacked steps)."""
+    window (round 6, ADVICE r5: a reward plug-in that reads `batch.meta[b]` sees the same thing on stacked and unstacked steps).
+    `frames` (optional, FrameDataset sets it): a list of length B whose entry b is `(pool, plan)` - the prompt's uint8 frame pool
+    on the device and the int64 index plan [T] with `pool[plan[t]]` = frame t of the video the policy scored - or None."""
 
-    def __init__(self, feats, txt, clip, mask, item_type="specific", meta=None):
+    def __init__(self, feats, txt, clip, mask, item_type="specific", meta=None, frames=None):
         B = feats.shape[0]
+        if frames is not None and (not isinstance(frames, list) or len(frames) != B):
+            raise ValueError(f"Batch.frames must be a list with one (pool, plan) entry per prompt (B={B})")
+        self.frames = frames
         if meta is None:
             meta = [None] * B
         elif not isinstance(meta, list):
@@ -78,6 +84,19 @@ class Batch:
         if meta is None or len(meta) != B:
             raise ValueError(f"Batch.meta must be a list with one entry per prompt (B={B})")
         self.feats, self.txt, self.clip, self.mask, self.item_type, self.meta = feats, txt, clip, mask, item_type, meta
+
+    def selected_frames(self, idx: torch.Tensor, spec) -> torch.Tensor:
+        """The frames the rollouts selected, through the reward model's image processor (`spec`: a
+        preprocess.PreprocessSpec): idx [B,G,k] int64 on the device (as `reward_model` receives it) -> [B,G,k,3,h,w] of
+        spec.out_dtype.  Replaces `video_inputs[0][ts_ids[1].cpu()]` + `image_processor.preprocess(...).to(device).to(dtype)`
+        (tspo_trainer.py:516,524) with one HIP call per prompt; the index composition plan[idx] happens on the device - `idx`
+        is never copied to the host and nothing synchronises."""
+        from .preprocess import select_frames
+        if self.frames is None or any(f is None for f in self.frames):
+            raise ValueError("this batch carries no frames (feature-level data set): selected_frames needs Batch.frames")
+        if idx.ndim != 3 or idx.shape[0] != len(self.frames):
+            raise ValueError(f"idx must be [B,G,k] with B={len(self.frames)}, got {tuple(idx.shape)}")
+        return torch.stack([select_frames(pool, plan[idx[b]], spec) for b, (pool, plan) in enumerate(self.frames)])
 
 
 class SyntheticFeatures:
@@ -131,6 +150,140 @@ class FeatureCacheDataset:
             pos = 0
 
 
+_ANSWER_STYLE_1 = 'Please provide your answer by stating the letter followed by the full option.'
+_ANSWER_STYLE_2 = 'Please respond with only the letter of the correct answer.'
+
+
+def problem_text(original_question: str) -> str:
+    """The text the CLIP text tower sees, derived from an annotation's `original_question` exactly as tspo_trainer.py:438-443
+    does: drop the image token and the two answer-style sentences, keep what precedes the first option ("\nA" form checked
+    first, then "\n(A)")."""
+    q = original_question.replace("<image>\n", "").replace(_ANSWER_STYLE_1, "").replace(_ANSWER_STYLE_2, "")
+    if "\nA" in original_question:
+        return q.split("\nA")[0]
+    if "\n(A)" in original_question:
+        return q.split("\n(A)")[0]
+    raise ValueError("original_question has no option list (neither '\\nA' nor '\\n(A)'): the reference leaves `problem` unset here")
+
+
+def load_npy_video(path: str, max_frames_num: int, fps: int, force_sample: bool):
+    """Default video reader of FrameDataset (no video decoder in the image): a uint8 [L,H,W,3] .npy file holding the frames
+    already sampled at `fps`; more than max_frames_num frames are thinned uniformly like the reference's load_video.  Same
+    signature and return shape as the reader io.FrameIdGenerator takes: (frames, frame_time, video_time, frame_idx)."""
+    arr = np.load(path, mmap_mode="r")
+    if arr.dtype != np.uint8 or arr.ndim != 4 or arr.shape[-1] != 3:
+        raise ValueError(f"{path}: expected uint8 [L,H,W,3], got {arr.dtype} {arr.shape}")
+    ids = np.arange(arr.shape[0])
+    if arr.shape[0] > max_frames_num or force_sample:
+        ids = np.linspace(0, arr.shape[0] - 1, max_frames_num, dtype=int)
+    return np.ascontiguousarray(arr[ids]), None, None, torch.from_numpy(ids)
+
+
+class FrameDataset:
+    """The training step from frames (tspo_trainer.py:456-498): items as the reference's annotation files give them (`video`,
+    `original_question`, `type`).  Per item: read <= 128 frames -> pool [video || 12 distractor clips] to the device ONCE ->
+    needle-in-a-haystack index plan (haystack.build_specific_plan; "general" items keep the video, all-true mask, :482) -> HIP
+    front end through the plan (preprocess.select_frames, CLIP spec, uint8) -> HIP CLIP encode -> clip score -> Batch with
+    `frames=[(pool, plan)]`.  The haystack is never materialised at source resolution.  The text feature comes from the CLIP
+    text tower of `model` (stock PyTorch).  `load_video(path, max_frames_num, fps, force_sample)` and
+    `distractors(n_clips, clip_len, like, seed)` are injectable (the reference's sample_real_frames needs a video corpus).
+    Random streams are seeded per (seed, global item index): a resumed run draws the haystacks a straight run draws.
+    `record=True` keeps (global item index, plan, mask) of every item prepared in `history` (off by default: it grows with
+    the run)."""
+
+    def __init__(self, items: Sequence[dict], model, clip_processor, video_root: str = "", load_video=None, distractors=None,
+                 seed: int = 0, device="cuda", sample_len: int = 50, n_distractor_clips: int = 12, max_frames_num: int = 128,
+                 record: bool = False):
+        from . import haystack
+        from .preprocess import PreprocessSpec
+        if not items:
+            raise ValueError("FrameDataset: no items")
+        ip = getattr(clip_processor, "image_processor", None)
+        spec = PreprocessSpec.from_image_processor(ip, out_dtype=torch.uint8) if ip is not None else None
+        if spec is None or spec.with_dtype(torch.float32) != PreprocessSpec.clip_default():
+            raise ValueError("FrameDataset: the CLIP processor is not configured like CLIP's default one - the on-device front end "
+                             "would not reproduce it (no fallback)")
+        self.items, self.model, self.proc, self.root = list(items), model, clip_processor, video_root
+        self.load_video = load_video or load_npy_video
+        self.distractors = distractors or haystack.synthetic_distractors
+        self.seed, self.dev, self.spec = int(seed), torch.device(device), spec
+        self.sample_len, self.n_clips, self.max_frames = sample_len, n_distractor_clips, max_frames_num
+        self.record, self.history = bool(record), []
+
+    def item_seed(self, gi: int) -> int:
+        return (self.seed * 1_000_003 + gi) % (2 ** 32)
+
+    def prepare(self, gi: int) -> Batch:
+        import random
+        from . import haystack
+        from .preprocess import select_frames
+        from .temporal_agent import _image_features, _pooled
+        it = self.items[gi % len(self.items)]
+        video = self.load_video(os.path.join(self.root, it["video"]), self.max_frames, 1, False)[0]
+        video = video if isinstance(video, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(video)))
+        L, sd = int(video.shape[0]), self.item_seed(gi)
+        if it.get("type", "specific") == "specific":
+            glen = min(L, self.sample_len)
+            pool = haystack.haystack_pool(video, self.distractors(self.n_clips, glen, video, seed=sd)).to(self.dev)
+            plan, mask = haystack.build_specific_plan(L, self.n_clips, sample_len=self.sample_len, rng=np.random.RandomState(sd),
+                                                      py_random=random.Random(sd))
+        else:
+            pool, plan, mask = video.to(self.dev), torch.arange(L), haystack.general_sample_mask(video)
+        if self.record:
+            self.history.append((gi, plan, mask))
+        plan_d = plan.to(self.dev)
+        inputs_text = self.proc(text=problem_text(it["original_question"]), return_tensors="pt", padding=True, truncation=True).to(self.dev)
+        with torch.no_grad():
+            txt = _pooled(self.model.get_text_features(**inputs_text)).float()[:1]
+            feats = _image_features(self.model, select_frames(pool, plan_d, self.spec))
+            clip = ops.clip_scores(txt[None], feats[None])
+        return Batch(feats[None], txt[None], clip, mask.to(self.dev)[None], it.get("type", "specific"),
+                     [{"video": it["video"], "item": gi, "n_video_frames": L}], frames=[(pool, plan_d)])
+
+    def batches(self, rank: int, world: int, bs: int, skip: int = 0) -> Iterator[Batch]:
+        """`skip` = micro-batches already consumed (resume): the item cursor advances, nothing is read or decoded for them."""
+        if bs != 1:
+            raise ValueError("FrameDataset: haystacks differ in length (T = 50 x (r + 12)): one prompt per micro-batch, like the "
+                             f"reference (per_device_train_batch_size 1), got {bs}")
+        i = int(skip)
+        while True:
+            yield self.prepare(i * world + rank)
+            i += 1
+
+
+class PretokenizedProcessor:
+    """CLIPProcessor stand-in for annotation files that carry the CLIP token ids of their problem text (`input_ids` next to
+    `original_question`): text -> those ids, so a run needs no tokenizer files; `image_processor` is a real CLIPImageProcessor."""
+
+    def __init__(self, items: Sequence[dict], image_processor):
+        self.image_processor = image_processor
+        self.ids = {problem_text(it["original_question"]): [int(t) for t in it["input_ids"]] for it in items}
+
+    def __call__(self, text=None, return_tensors="pt", **kw):
+        from transformers import BatchEncoding
+        ids = torch.tensor([self.ids[text][:77]])
+        return BatchEncoding({"input_ids": ids, "attention_mask": torch.ones_like(ids)})
+
+
+def frame_dataset_from_dir(frame_dir: str, model_dir: Optional[str], seed: int, device, record: bool = False) -> FrameDataset:
+    """`--frame-dir <dir>`: `<dir>/items.json` (a list of annotation items; `video` relative to <dir>) + uint8 [L,H,W,3] `.npy`
+    videos.  The TSPOModel (CLIP towers; its selector is the policy that trains) is loaded from `model_dir` (default
+    `<dir>/model`), and so is the CLIP processor - unless every item carries `input_ids`, then no tokenizer is needed."""
+    from transformers import CLIPImageProcessor
+    from .temporal_agent import TSPOModel
+    with open(os.path.join(frame_dir, "items.json")) as f:
+        items = json.load(f)
+    model_dir = model_dir or os.path.join(frame_dir, "model")
+    model = TSPOModel.from_pretrained(model_dir, torch_dtype=torch.float32).to(device).eval()
+    if all("input_ids" in it for it in items):
+        has_cfg = os.path.exists(os.path.join(model_dir, "preprocessor_config.json"))
+        proc = PretokenizedProcessor(items, CLIPImageProcessor.from_pretrained(model_dir) if has_cfg else CLIPImageProcessor())
+    else:
+        from transformers import CLIPProcessor
+        proc = CLIPProcessor.from_pretrained(model_dir)
+    return FrameDataset(items, model, proc, video_root=frame_dir, seed=seed, device=device, record=record)
+
+
 def _stackable(window: List[Batch]) -> bool:
     a = window[0]
     return len(window) > 1 and all(b.feats.shape == a.feats.shape and b.txt.shape == a.txt.shape and b.mask.shape == a.mask.shape
@@ -139,7 +292,9 @@ def _stackable(window: List[Batch]) -> bool:
 
 def _stack(window: List[Batch]) -> Batch:
     return Batch(torch.cat([b.feats for b in window]), torch.cat([b.txt for b in window]), torch.cat([b.clip for b in window]),
-                 torch.cat([b.mask for b in window]), window[0].item_type, [m for b in window for m in b.meta])
+                 torch.cat([b.mask for b in window]), window[0].item_type, [m for b in window for m in b.meta],
+                 None if all(b.frames is None for b in window) else
+                 [f for b in window for f in (b.frames if b.frames is not None else [None] * b.feats.shape[0])])
 
 
 def mask_reward_model(idx: torch.Tensor, batch: Batch) -> torch.Tensor:
@@ -270,6 +425,9 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--features", default=None, help="directory of feature-cache .pth files (default: synthetic features)")
     ap.add_argument("--frames", type=int, default=512, help="T of the synthetic features")
+    ap.add_argument("--frame-dir", default=None, help="train from frames: <dir>/items.json (video, original_question, type[, input_ids]) "
+                                                      "+ uint8 [L,H,W,3] .npy videos; the policy is the selector of --model")
+    ap.add_argument("--model", default=None, help="TSPOModel directory for --frame-dir (default: <frame-dir>/model)")
     ap.add_argument("--backend", default="nccl")
     ap.add_argument("--gpus", type=int, default=0, help="ranks to run; without a launcher (no WORLD_SIZE) the driver spawns them itself")
     ap.add_argument("--no-resume", action="store_true")
@@ -283,9 +441,27 @@ def main(argv=None):
         import sys
         return tdist.self_spawn(a.gpus, [""] + list(sys.argv[1:] if argv is None else argv), module="tspo_amd.train")
     cfg = TrainConfig(**{k: getattr(a, k) for k in asdict(TrainConfig())})
-    data = FeatureCacheDataset(a.features) if a.features else SyntheticFeatures(T=a.frames, D=cfg.dim, seed=cfg.seed)
-    m = train(cfg, data, backend=a.backend, resume=not a.no_resume,
-              log=lambda r: print(json.dumps(r), flush=True) if int(os.environ.get("RANK", "0")) == 0 else None)
+    flat = None
+    if a.frame_dir:
+        if a.features:
+            ap.error("--frame-dir and --features exclude each other")
+        local = int(os.environ.get("LOCAL_RANK", "0"))
+        dev = torch.device("cuda", local if torch.cuda.device_count() > local else 0)
+        data = frame_dataset_from_dir(a.frame_dir, a.model, cfg.seed, dev, record=True)
+        flat = data.model.selector.flatten_parameters(dev).detach().clone()
+        if flat.numel() != ops.flat_offsets(cfg.dim)["__total__"][0]:
+            ap.error(f"--dim {cfg.dim} does not match the selector of the model")
+    else:
+        data = FeatureCacheDataset(a.features) if a.features else SyntheticFeatures(T=a.frames, D=cfg.dim, seed=cfg.seed)
+    rank = int(os.environ.get("RANK", "0"))
+    m = train(cfg, data, flat=flat, backend=a.backend, resume=not a.no_resume,
+              log=lambda r: print(json.dumps(r), flush=True) if rank == 0 else None)
+    if a.frame_dir and m:
+        # per-rank record of the run: which items this rank drew (and the length of their haystacks) and the replica's weights
+        import hashlib
+        with open(os.path.join(cfg.output_dir, f"frames.rank{rank}.json"), "w") as f:
+            json.dump({"items": [[gi, int(plan.numel())] for gi, plan, _ in data.history],
+                       "flat_sha256": hashlib.sha256(m["flat"].cpu().numpy().tobytes()).hexdigest()}, f)
     return 0 if m else 1
 
 
