@@ -346,6 +346,36 @@ int tspo_clip_vit_forward(const tspo_clip_weights* w, const void* pixels, int pi
 int tspo_clip_vit_forward_ex(const tspo_clip_weights* w, const void* pixels, int pixel_dtype, int n_frames,
                              float* feat, void* workspace, size_t workspace_bytes, tspo_stream_t stream, int flags);
 
+/* Whether an encode of n_frames takes the LayerNorm-folded path (when TSPO_CLIP_NO_LN_FOLD is not given): 1 = folds, 0 = does not;
+ * the very function the forward entries decide with (both folded GEMMs of a layer must be problems of the persistent kernel), so a
+ * caller that keeps folded weights between calls (TSPO_CLIP_FOLD_CACHED) need not restate it.  Monotone in n_frames.  Touches no
+ * device.  NULL or unusable config / n_frames < 1: TSPO_EINVAL (negative).                                                      */
+int tspo_clip_will_fold(const tspo_clip_config* cfg, int n_frames);
+
+/* How tspo_clip_vit_forward_chunked cuts n_frames into chunks of at most chunk_frames: writes the chunk sizes (in frame order) to
+ * HOST array sizes[0 .. count-1] and returns count (> 0), or a negative error.  A pure function of its arguments; touches no device.
+ *   - the sizes sum to n_frames, every size is <= chunk_frames, count = ceil(n_frames / chunk_frames);
+ *   - every size but the last is a multiple of 64 frames (whole 64-row blocks of the GEMMs: the rows of such a chunk meet the
+ *     persistent kernel's 64x64 remainder phase only where the one-call encode's rows do);
+ *   - if tspo_clip_will_fold(cfg, n_frames), every chunk folds too (CLIP-L/14: no chunk under 64 frames) - no tail falls onto the
+ *     small-batch path, which computes other bits and is slower.
+ * TSPO_EINVAL with a message: n_frames < 1, chunk_frames < 1, chunk_frames below the smallest batch that folds (for a config that
+ * folds at all), cap < count, and the (n_frames, chunk_frames) pairs for which NO list of sizes meets all the clauses above (e.g.
+ * CLIP-L/14, 65 frames in chunks of at most 64; 50 000 frames in exactly 50 chunks of at most 1000).  A chunk_frames that is a
+ * multiple of 64 and at least twice the smallest folding batch rounded up to 64 always has a plan.                                 */
+int tspo_clip_chunk_plan(const tspo_clip_config* cfg, int n_frames, int chunk_frames, int* sizes, int cap);
+
+/* tspo_clip_vit_forward_ex run over tspo_clip_chunk_plan(cfg, n_frames, chunk_frames), chunk after chunk on `stream`, for pixels
+ * that are already on the device: chunk i reads its frames of `pixels` and writes its rows of feat [n_frames, proj].  The
+ * workspace need only hold the LARGEST chunk: tspo_clip_workspace_bytes(cfg, max(sizes)) - bounded memory for videos of any
+ * length.  The LayerNorm fold runs on the first chunk (unless the caller's own TSPO_CLIP_FOLD_CACHED vouches for this workspace
+ * already), the later chunks run with TSPO_CLIP_FOLD_CACHED; TSPO_CLIP_PRUNE_LAST / TSPO_CLIP_NO_LN_FOLD pass through to every
+ * chunk.  Pointers, flags, the plan and the workspace size are validated before any device work.  chunk_frames >= n_frames is
+ * exactly one tspo_clip_vit_forward_ex call.  Chunks whose sizes are multiples of 64 frames give the bits of the one-call encode;
+ * otherwise the features depend on the plan through the GEMM remainder phase only (as one-call encodes of different n_frames do). */
+int tspo_clip_vit_forward_chunked(const tspo_clip_weights* w, const void* pixels, int pixel_dtype, int n_frames, int chunk_frames,
+                                  float* feat, void* workspace, size_t workspace_bytes, tspo_stream_t stream, int flags);
+
 /* Same computation, with a hipEvent recorded on `stream` after every kernel launch; synchronises on the
  * last event (profiling entry point - the only one that waits) and returns in HOST array host_ms6:
  * [0] GEMM ms, [1] attention ms, [2] LayerNorm ms, [3] patch gather ms, [4] total ms, [5] number of GEMM

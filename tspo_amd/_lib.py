@@ -74,6 +74,9 @@ SIGNATURES = {
     "tspo_clip_workspace_bytes": (_sz, [C.POINTER(ClipConfig), _i]),
     "tspo_clip_vit_forward": (_i, [C.POINTER(ClipWeights), _p, _i, _i, _p, _p, _sz, _p]),
     "tspo_clip_vit_forward_ex": (_i, [C.POINTER(ClipWeights), _p, _i, _i, _p, _p, _sz, _p, _i]),
+    "tspo_clip_will_fold": (_i, [C.POINTER(ClipConfig), _i]),
+    "tspo_clip_chunk_plan": (_i, [C.POINTER(ClipConfig), _i, _i, C.POINTER(C.c_int), _i]),
+    "tspo_clip_vit_forward_chunked": (_i, [C.POINTER(ClipWeights), _p, _i, _i, _i, _p, _p, _sz, _p, _i]),
     "tspo_clip_vit_profile": (_i, [C.POINTER(ClipWeights), _p, _i, _i, _p, _p, _sz, _p, C.POINTER(C.c_float), _i]),
     "tspo_preprocess_workspace_bytes": (_sz, [_i, _i, _i]),
     "tspo_preprocess_frames": (_i, [_p, _i, _i, _i, _i, _p, _p, _i, _i, _p, _p, _i, _i, _i, _i, _p, _p, _sz, _p]),

@@ -6,6 +6,7 @@
 // Replaces transformers' CLIPVisionTransformer + visual_projection as called
 // by the reference at model/temporal_agent.py:166, tspo_trainer.py:401.
 #include "gemm_bf16.h"
+#include <vector>
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
@@ -1025,6 +1026,82 @@ extern "C" size_t tspo_clip_workspace_bytes(const tspo_clip_config* cfg, int n_f
   return clip_carve(nullptr, *cfg, n_frames).bytes;
 }
 
+// The fold decision of an encode of n frames: the LayerNorm-folded epilogues exist only in the persistent 256x256 kernel, so the
+// layer's GEMM shapes must be "big" problems (gemm_bf16_is_big).  The ONE place it is written down: clip_forward_impl,
+// tspo_clip_will_fold and the chunk planner all call this.
+static bool clip_folds(const tspo_clip_config& c, long n_frames) {
+  const int gw = c.image / c.patch;
+  const long M = n_frames * ((long)gw * gw + 1);
+  return c.layers > 0 && tspo::gemm_bf16_is_big(M, c.hidden, c.hidden) && tspo::gemm_bf16_is_big(M, c.hidden, c.mlp);
+}
+
+// Smallest batch that folds (clip_folds is monotone in n_frames), or 0 for a config that never folds.
+static int clip_min_fold_frames(const tspo_clip_config& c) {
+  const int gw = c.image / c.patch;
+  long hi = ((1L << 31) - 1) / ((long)gw * gw + 1);   // the forward entries take M < 2^31 rows
+  if (!clip_folds(c, hi)) return 0;
+  long lo = 1;
+  while (lo < hi) {
+    const long mid = lo + (hi - lo) / 2;
+    if (clip_folds(c, mid)) hi = mid; else lo = mid + 1;
+  }
+  return (int)lo;
+}
+
+extern "C" int tspo_clip_will_fold(const tspo_clip_config* cfg, int n_frames) {
+  TSPO_REQUIRE(cfg, "clip_will_fold: null config");
+  TSPO_REQUIRE(n_frames >= 1, "clip_will_fold: n_frames=%d", n_frames);
+  TSPO_REQUIRE(cfg->patch >= 1 && cfg->image >= cfg->patch, "clip_will_fold: image=%d patch=%d", cfg->image, cfg->patch);
+  return clip_folds(*cfg, n_frames) ? 1 : 0;
+}
+
+// The chunk plan (include/tspo_hip.h).  With b = 64 frames: count = ceil(n / chunk); the first count-1 chunks hold j blocks of b
+// frames in all, each between ceil(f / b) and floor(chunk / b) blocks, and the last chunk holds n - j b frames in [f, chunk], where
+// f = the smallest folding batch when n frames fold, else 1.  The largest such j is taken (full leading chunks, the smallest tail
+// that still folds) and spread evenly.  Returns count and, when sizes != nullptr, writes them; *largest gets the largest chunk.
+static int clip_plan(const tspo_clip_config& c, int n, int chunk, int* sizes, int cap, int* largest) {
+  TSPO_REQUIRE(n >= 1, "clip_chunk_plan: n_frames=%d", n);
+  TSPO_REQUIRE(chunk >= 1, "clip_chunk_plan: chunk_frames=%d", chunk);
+  // (only the geometry the fold decision reads is needed here, as for tspo_clip_workspace_bytes; the forward checks the rest)
+  TSPO_REQUIRE(c.patch >= 1 && c.image >= c.patch, "clip_chunk_plan: image=%d patch=%d", c.image, c.patch);
+  const int gw = c.image / c.patch;
+  TSPO_REQUIRE((long)n * ((long)gw * gw + 1) < (1L << 31), "clip_chunk_plan: n_frames=%d too large", n);
+  const int fmin = clip_min_fold_frames(c);
+  TSPO_REQUIRE(fmin == 0 || chunk >= fmin,
+               "clip_chunk_plan: chunk_frames=%d is below the %d frames at which this encoder folds its LayerNorms - such chunks "
+               "would take the slower small-batch path and compute other bits", chunk, fmin);
+  const long b = 64;
+  const long f = clip_folds(c, n) ? fmin : 1;
+  const long count = ((long)n + chunk - 1) / chunk;
+  TSPO_REQUIRE(sizes && cap >= count, "clip_chunk_plan: %ld chunks do not fit sizes[%d]", count, sizes ? cap : 0);
+  if (count == 1) {
+    sizes[0] = n;
+    if (largest) *largest = n;
+    return 1;
+  }
+  const long bmax = chunk / b, bmin = (f + b - 1) / b, lead = count - 1;
+  long j = (n - f) / b;
+  if (j > lead * bmax) j = lead * bmax;
+  TSPO_REQUIRE(bmax >= bmin && j >= lead * bmin && n - j * b <= chunk,
+               "clip_chunk_plan: no plan cuts %d frames into %ld chunks of at most %d frames with every chunk but the last a multiple "
+               "of 64 frames and none under %ld frames - use a chunk_frames that is a multiple of 64 and at least %ld",
+               n, count, chunk, f, 2 * bmin * b);
+  const long base = j / lead, extra = j % lead;
+  int mx = 0;
+  for (long i = 0; i < count; ++i) {
+    const int s = (int)(i < lead ? (base + (i < extra ? 1 : 0)) * b : n - j * b);
+    sizes[i] = s;
+    if (s > mx) mx = s;
+  }
+  if (largest) *largest = mx;
+  return (int)count;
+}
+
+extern "C" int tspo_clip_chunk_plan(const tspo_clip_config* cfg, int n_frames, int chunk_frames, int* sizes, int cap) {
+  TSPO_REQUIRE(cfg, "clip_chunk_plan: null config");
+  return clip_plan(*cfg, n_frames, chunk_frames, sizes, cap, nullptr);
+}
+
 extern "C" int tspo_gemm_bf16(const void* A, const void* W, const float* bias, const void* residual, void* C,
                               int out_dtype, int M, int N, int K, int act, tspo_stream_t stream) {
   TSPO_REQUIRE(A && W && C, "gemm_bf16: null pointer");
@@ -1107,7 +1184,7 @@ static int clip_forward_impl(const tspo_clip_weights* w, const void* pixels, int
   if (int e = run_ln(b.x, b.x, w->pre_g, w->pre_b, M, C, C, C, c.ln_eps, st)) return e;
   prof.tick(PK_LN);
   // 4. transformer blocks.  Large batches: LayerNorm folded into the GEMMs (see ln_fold_kernel); otherwise stand-alone passes.
-  const bool fold = !no_fold && c.layers > 0 && tspo::gemm_bf16_is_big(M, C, C) && tspo::gemm_bf16_is_big(M, C, c.mlp);
+  const bool fold = !no_fold && clip_folds(c, n_frames);
   if (fold) {
     hipLaunchKernelGGL(row_stats_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, b.x, M, C, c.ln_eps, b.stats);
     if (int e = tspo::check_launch("row_stats")) return e;
@@ -1228,6 +1305,45 @@ extern "C" int tspo_clip_vit_forward_ex(const tspo_clip_weights* w, const void* 
                                         int flags) {
   Prof prof;
   return clip_forward_impl(w, pixels, pixel_dtype, n_frames, feat, workspace, workspace_bytes, stream, flags, prof);
+}
+
+extern "C" int tspo_clip_vit_forward_chunked(const tspo_clip_weights* w, const void* pixels, int pixel_dtype, int n_frames,
+                                             int chunk_frames, float* feat, void* workspace, size_t workspace_bytes,
+                                             tspo_stream_t stream, int flags) {
+  TSPO_REQUIRE(w && pixels && feat && workspace, "clip_vit_forward_chunked: null pointer");
+  TSPO_REQUIRE((flags & ~(TSPO_CLIP_NO_LN_FOLD | TSPO_CLIP_PRUNE_LAST | TSPO_CLIP_FOLD_CACHED)) == 0,
+               "clip_vit_forward_chunked: unknown flags 0x%x", flags);
+  size_t px_bytes;
+  switch (pixel_dtype) {
+    case TSPO_F32: px_bytes = 4; break;
+    case TSPO_BF16: case TSPO_F16: px_bytes = 2; break;
+    case TSPO_U8: px_bytes = 1; break;
+    default: return tspo::set_err(TSPO_EINVAL, "clip_vit_forward_chunked: bad pixel_dtype %d", pixel_dtype);
+  }
+  const tspo_clip_config& c = w->cfg;
+  if (int e = clip_check_cfg(c)) return e;
+  TSPO_REQUIRE(n_frames >= 1 && chunk_frames >= 1, "clip_vit_forward_chunked: n_frames=%d chunk_frames=%d", n_frames, chunk_frames);
+  const long count = ((long)n_frames + chunk_frames - 1) / chunk_frames;
+  std::vector<int> sizes((size_t)count);   // host memory
+  int largest = 0;
+  const int nc = clip_plan(c, n_frames, chunk_frames, sizes.data(), (int)count, &largest);
+  if (nc < 0) return nc;
+  const size_t need = clip_carve(nullptr, c, largest).bytes;
+  if (workspace_bytes < need)
+    return tspo::set_err(TSPO_EWORKSPACE, "clip_vit_forward_chunked: workspace %zu < %zu (chunks of up to %d frames)",
+                         workspace_bytes, need, largest);
+  px_bytes *= (size_t)3 * c.image * c.image;
+  Prof prof;
+  size_t lo = 0;
+  for (int i = 0; i < nc; ++i) {
+    // every chunk folds when the first does (the plan), and the folded weights sit at offsets that do not depend on the batch
+    const int fl = flags | (i > 0 ? TSPO_CLIP_FOLD_CACHED : 0);
+    if (int e = clip_forward_impl(w, (const char*)pixels + lo * px_bytes, pixel_dtype, sizes[i], feat + lo * c.proj, workspace,
+                                  workspace_bytes, stream, fl, prof))
+      return e;
+    lo += (size_t)sizes[i];
+  }
+  return TSPO_OK;
 }
 
 extern "C" int tspo_clip_vit_forward(const tspo_clip_weights* w, const void* pixels, int pixel_dtype, int n_frames,

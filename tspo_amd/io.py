@@ -115,12 +115,15 @@ class FrameIdGenerator:
     cache miss -> decode the video (`load_video`, a plug-in: decord is outside this package), `extract_feature`, save the
     .pth cache; cache hit -> load it, move to the model's device and dtype; then `temporal_sampling` (bin-max for
     VideoMME, top-k otherwise, window 12) unless the video has no more than `sample_num` frames; returns the selected
-    absolute frame numbers as floats."""
+    absolute frame numbers as floats.  `encode_chunk_frames` (default None: the model's own setting): the harness samples up
+    to 50 000 frames per video; an int makes `extract_feature` encode them in chunks of at most that many frames
+    (`TSPOModel.encode_chunk_frames`, set for the duration of the call)."""
 
     def __init__(self, model, clip_processor, save_root: str, sample_num: int = 64,
-                 load_video: Optional[Callable] = None):
+                 load_video: Optional[Callable] = None, encode_chunk_frames: Optional[int] = None):
         self.tspo_model, self.clip_processor = model, clip_processor
         self.save_root, self.sample_num, self.load_video = save_root, sample_num, load_video
+        self.encode_chunk_frames = encode_chunk_frames
         self.cache_hits = self.cache_misses = 0
 
     @staticmethod
@@ -138,7 +141,15 @@ class FrameIdGenerator:
             if self.load_video is None:
                 raise FileNotFoundError(f"{path} is not cached and no load_video plug-in was given")
             video, _, _, sampled_idx = self.load_video(video_path, max_frames_num=50000, fps=1, force_sample=False)
-            image, text, clip = model.extract_feature(self.clip_processor, video, problem)
+            if self.encode_chunk_frames is None:
+                image, text, clip = model.extract_feature(self.clip_processor, video, problem)
+            else:
+                before = getattr(model, "encode_chunk_frames", None)
+                model.encode_chunk_frames = self.encode_chunk_frames
+                try:
+                    image, text, clip = model.extract_feature(self.clip_processor, video, problem)
+                finally:
+                    model.encode_chunk_frames = before
             save_feature_cache(path, image, text, clip, sampled_idx)
             sampled_idx = torch.as_tensor(sampled_idx)
             self.cache_misses += 1

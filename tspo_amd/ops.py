@@ -433,15 +433,11 @@ class ClipVitWeights:
         return ws
 
     def library_folds(self, n_frames: int) -> bool:
-        """Whether an encode of n_frames takes the LayerNorm-folded path at all (mirrors csrc/clip_vit.hip: both folded GEMMs must be
-        "big" problems, csrc/gemm_bf16.hip gemm_bf16_is_big - checked against the library's behaviour by tests/test_gpu_ops.py)."""
-        c = self.cfg
-        S = (c["image"] // c["patch"]) ** 2 + 1
-        M = n_frames * S
-
-        def big(N, K):
-            return M * N >= 256 ** 3 and K >= 128 and N <= 4096
-        return c["layers"] > 0 and big(c["hidden"], c["hidden"]) and big(c["hidden"], c["mlp"])
+        """Whether an encode of n_frames takes the LayerNorm-folded path at all: the library's own decision
+        (`tspo_clip_will_fold`, the function csrc/clip_vit.hip decides with)."""
+        rc = _lib.lib().tspo_clip_will_fold(C.byref(self.struct.cfg), int(n_frames))
+        check(min(rc, 0), "tspo_clip_will_fold")
+        return rc == 1
 
 
 def _clip_flags(fold_layernorm: bool, prune_last_layer: bool, fold_cached: bool = False) -> int:
@@ -483,6 +479,58 @@ def clip_vit_forward(w: ClipVitWeights, pixels: torch.Tensor, out: Optional[torc
     check(_lib.lib().tspo_clip_vit_forward_ex(C.byref(w.struct), _ptr(px), _PIX_DTYPES[px.dtype], N, _ptr(feat), _ptr(ws),
                                               ws.numel(), _stream(), _clip_flags(fold_layernorm, prune_last_layer, cached)),
           "tspo_clip_vit_forward")
+    if fold_layernorm and key is not None:
+        w._fold_key = key
+    return feat
+
+
+def _clip_cfg_struct(w_or_cfg):
+    if isinstance(w_or_cfg, ClipVitWeights):
+        return w_or_cfg.struct.cfg
+    if isinstance(w_or_cfg, _lib.ClipConfig):
+        return w_or_cfg
+    c = w_or_cfg
+    return _lib.ClipConfig(c["hidden"], c["layers"], c["heads"], c["mlp"], c["patch"], c["image"], c["proj"],
+                           float(c.get("ln_eps", 1e-5)))
+
+
+def clip_chunk_plan(w_or_cfg, n_frames: int, chunk_frames: int) -> list:
+    """The chunk sizes `clip_vit_forward_chunked` cuts n_frames into (`tspo_clip_chunk_plan`: they sum to n_frames, none above
+    chunk_frames, all but the last multiples of 64 frames, and none below the fold threshold when n_frames folds).  `w_or_cfg`: a
+    ClipVitWeights or a config dict.  ValueError where the library finds no plan (its message says which chunk_frames always work)."""
+    n = int(n_frames)
+    sizes = (C.c_int * max(1, n))()            # count <= n_frames
+    rc = _lib.lib().tspo_clip_chunk_plan(C.byref(_clip_cfg_struct(w_or_cfg)), n, int(chunk_frames), sizes, len(sizes))
+    check(min(rc, 0), "tspo_clip_chunk_plan")
+    return list(sizes[:rc])
+
+
+def clip_vit_forward_chunked(w: ClipVitWeights, pixels: torch.Tensor, chunk_frames: int, out: Optional[torch.Tensor] = None,
+                             fold_layernorm: bool = True, prune_last_layer: bool = False) -> torch.Tensor:
+    """clip_vit_forward over device-resident pixels [N,3,H,W] in chunks of at most chunk_frames frames (`clip_chunk_plan`), in ONE
+    library call (`tspo_clip_vit_forward_chunked`): the workspace holds the largest chunk only, so a video of any length encodes in
+    bounded memory (the whole-video workspace is ~5 MB per CLIP-L/14 frame).  The LayerNorm fold runs once, on the first chunk (or
+    not at all when this workspace already holds it).  Chunk sizes that are multiples of 64 frames give the bits of
+    clip_vit_forward(pixels); otherwise the features depend on the plan through the GEMM remainder phase only."""
+    _need_gpu(pixels)
+    if pixels.dtype not in _PIX_DTYPES:
+        raise TypeError(f"unsupported pixel dtype {pixels.dtype}")
+    px = pixels.contiguous()
+    N = px.shape[0]
+    cfg = w.cfg
+    if tuple(px.shape[1:]) != (3, cfg["image"], cfg["image"]):
+        raise ValueError(f"pixels must be [N,3,{cfg['image']},{cfg['image']}], got {tuple(px.shape)}")
+    plan = clip_chunk_plan(w, N, chunk_frames)
+    ws = w._workspace(max(plan))
+    feat = out if out is not None else torch.empty((N, cfg["proj"]), dtype=torch.float32, device=px.device)
+    if feat.shape != (N, cfg["proj"]) or feat.dtype != torch.float32 or not feat.is_contiguous():
+        raise ValueError(f"out must be a contiguous float32 [{N}, {cfg['proj']}] tensor")
+    key = _fold_key(w, ws, N)                  # N folds <=> every chunk of the plan folds
+    cached = fold_layernorm and key is not None and w._fold_key == key
+    check(_lib.lib().tspo_clip_vit_forward_chunked(C.byref(w.struct), _ptr(px), _PIX_DTYPES[px.dtype], N, int(chunk_frames),
+                                                   _ptr(feat), _ptr(ws), ws.numel(), _stream(),
+                                                   _clip_flags(fold_layernorm, prune_last_layer, cached)),
+          "tspo_clip_vit_forward_chunked")
     if fold_layernorm and key is not None:
         w._fold_key = key
     return feat

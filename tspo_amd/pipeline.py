@@ -23,7 +23,7 @@ from . import ops
 class FrameScorer:
     def __init__(self, clip_weights: ops.ClipVitWeights, selector_flat: torch.Tensor, dim: int = 768, heads: int = 8,
                  window_size: int = 12, score_tau: float = 0.025, fold_layernorm: bool = True,
-                 prune_last_layer: bool = False, selector_precision: str = "fp32"):
+                 prune_last_layer: bool = False, selector_precision: str = "fp32", encode_chunk_frames: Optional[int] = None):
         # selector_precision: "fp32" (default; greedy indices identical to the fp32 oracle) or "bf16" - the reference's own inference
         # precision (gen_id_tspo.py:55): bf16 GEMM operands, fp32 accumulation (ops.selector_forward(precision="bf16"))
         ops._sel_flags(selector_precision, forward=True)
@@ -31,9 +31,15 @@ class FrameScorer:
         self.clip, self.flat = clip_weights, selector_flat
         self.dim, self.heads, self.window, self.tau = dim, heads, window_size, score_tau
         self.fold_layernorm, self.prune_last_layer = fold_layernorm, prune_last_layer   # encoder options (ops.clip_vit_forward)
+        # None: all frames of a call in one encode.  An int: in chunks of at most that many frames, the encoder workspace sized
+        # for the largest chunk (ops.clip_vit_forward_chunked) - long videos; with shard_frames, each rank chunks its own share
+        self.encode_chunk_frames = encode_chunk_frames
         self._sel_ws = None
 
     def _encode(self, px: torch.Tensor) -> torch.Tensor:
+        if self.encode_chunk_frames is not None:
+            return ops.clip_vit_forward_chunked(self.clip, px, int(self.encode_chunk_frames), fold_layernorm=self.fold_layernorm,
+                                                prune_last_layer=self.prune_last_layer)
         return ops.clip_vit_forward(self.clip, px, fold_layernorm=self.fold_layernorm, prune_last_layer=self.prune_last_layer)
 
     def encode(self, pixels: torch.Tensor, shard_frames: bool = False, group=None) -> torch.Tensor:

@@ -331,6 +331,94 @@ def preprocess_frames(frames: torch.Tensor, size: int = 224) -> torch.Tensor:
     return select_frames(frames, None, PreprocessSpec.clip_default(size, torch.uint8), what="preprocess_frames")
 
 
+class _StreamedEncodeState:
+    """What `encode_frames_streamed` keeps between calls on a ClipVitWeights: its ONE side stream, the two pinned staging
+    buffers, the two device raw-chunk buffers and, per buffer pair, the event of the last copy out of the staging buffer and of
+    the last kernel that read the raw buffer (pinning host memory costs more than the copy it serves, so it is done once)."""
+
+    def __init__(self, device):
+        self.stream = torch.cuda.Stream(device=device)
+        self.staging = [None, None]
+        self.raw = [None, None]
+        self.copied = [torch.cuda.Event(), torch.cuda.Event()]      # H2D copy out of staging[b] / into raw[b] has finished
+        self.consumed = [torch.cuda.Event(), torch.cuda.Event()]    # the preprocessing that read raw[b] has finished
+
+    def buffers(self, b: int, nbytes: int, device, current):
+        if self.staging[b] is None or self.staging[b].numel() < nbytes:
+            self.copied[b].synchronize()                            # nothing still reads the buffers that are let go
+            self.consumed[b].synchronize()
+            self.staging[b] = torch.empty((nbytes,), dtype=torch.uint8, pin_memory=True)
+            self.raw[b] = torch.empty((nbytes,), dtype=torch.uint8, device=device)
+            self.stream.wait_stream(current)                        # the allocator hands out memory in `current`'s order
+        self.raw[b].record_stream(current)
+        return self.staging[b], self.raw[b]
+
+
+def encode_frames_streamed(clip_weights, frames, chunk_frames: int, spec: Optional[PreprocessSpec] = None,
+                           out: Optional[torch.Tensor] = None, fold_layernorm: bool = True,
+                           prune_last_layer: bool = False) -> torch.Tensor:
+    """Raw uint8 video frames -> CLIP features f32 [T, proj] on the encoder's device, chunk by chunk of
+    `ops.clip_chunk_plan(clip_weights, T, chunk_frames)`, for frames that live in HOST memory: numpy or a CPU tensor, [T,H,W,3]
+    or [T,3,H,W], pageable or pinned.  Per chunk: host copy into one of two pinned staging buffers -> asynchronous copy to the
+    device on one side stream (owned by `clip_weights`, created on first use) -> event -> on the caller's current stream
+    `select_frames(chunk, None, spec)` and `tspo_clip_vit_forward_ex` into out[lo:hi].  The copy of chunk i+1 runs while chunk i
+    computes; a staging / raw buffer is reused only after an event shows its consumer has finished.  Device memory: two raw
+    chunks, one preprocessed chunk and the encoder workspace of the largest chunk - independent of T.  No threads are started.
+    `spec`: the image processor (default: CLIP's, uint8 output - the encoder normalises in its patch gather); its output size
+    must be the encoder's image size.  Frames that are already on the device skip the copies and take the same loop.
+    NOT capturable in a graph: it copies on the host and waits on events from the host.  Bitwise equal to `select_frames` of
+    the whole video followed by `ops.clip_vit_forward_chunked` with the same chunk_frames."""
+    from . import ops
+    cfg = clip_weights.cfg
+    if spec is None:
+        spec = PreprocessSpec.clip_default(cfg["image"], torch.uint8)
+    if tuple(spec.out_hw) != (cfg["image"], cfg["image"]):
+        raise ValueError(f"encode_frames_streamed: spec produces {spec.out_hw}, the encoder takes {cfg['image']}x{cfg['image']}")
+    fr = frames if isinstance(frames, torch.Tensor) else torch.from_numpy(np.asarray(frames))
+    _frame_layout(fr, "encode_frames_streamed")
+    T = int(fr.shape[0])
+    dev = clip_weights.device
+    plan = ops.clip_chunk_plan(clip_weights, T, chunk_frames)
+    feat = out if out is not None else torch.empty((T, cfg["proj"]), dtype=torch.float32, device=dev)
+    if tuple(feat.shape) != (T, cfg["proj"]) or feat.dtype != torch.float32 or not feat.is_contiguous() or not feat.is_cuda:
+        raise ValueError(f"encode_frames_streamed: out must be a contiguous float32 [{T}, {cfg['proj']}] tensor on the GPU")
+    clip_weights._workspace(max(plan))         # sized once for the largest chunk: the per-chunk encodes below share it (and its fold)
+
+    def encode(raw_chunk, lo, hi, read_event=None):
+        px = select_frames(raw_chunk, None, spec, what="encode_frames_streamed")
+        if read_event is not None:
+            read_event.record(torch.cuda.current_stream(dev))     # the raw chunk has no reader after this point
+        ops.clip_vit_forward(clip_weights, px, out=feat[lo:hi], fold_layernorm=fold_layernorm, prune_last_layer=prune_last_layer)
+
+    lo = 0
+    if fr.is_cuda:
+        for n in plan:
+            encode(fr[lo:lo + n], lo, lo + n)
+            lo += n
+        return feat
+    st = getattr(clip_weights, "_streamed", None)
+    if st is None:
+        st = clip_weights._streamed = _StreamedEncodeState(dev)
+    with torch.cuda.device(dev):
+        cur = torch.cuda.current_stream(dev)
+        per_frame = int(fr[0].numel())
+        for i, n in enumerate(plan):
+            b = i & 1
+            staging, raw = st.buffers(b, max(plan) * per_frame, dev, cur)
+            st.copied[b].synchronize()                               # the copy of chunk i-2 out of this staging buffer is done
+            host = staging[:n * per_frame].view(n, *fr.shape[1:])
+            host.copy_(fr[lo:lo + n])
+            chunk = raw[:n * per_frame].view(n, *fr.shape[1:])
+            st.stream.wait_event(st.consumed[b])                     # chunk i-2 has been read out of this raw buffer
+            with torch.cuda.stream(st.stream):
+                chunk.copy_(host, non_blocking=True)
+                st.copied[b].record(st.stream)
+            cur.wait_event(st.copied[b])
+            encode(chunk, lo, lo + n, st.consumed[b])                # launches only: the host goes on to stage chunk i+1
+            lo += n
+    return feat
+
+
 def processor_is_default_clip(image_processor, size: int = 224) -> bool:
     """True when a (HF) CLIPImageProcessor is configured exactly like openai/clip-vit-large-patch14's, i.e. when the
     on-device path is equivalent to calling it."""

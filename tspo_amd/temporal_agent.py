@@ -248,10 +248,10 @@ class MultiModal_Align(nn.Module):
         return scores, attn
 
 
-def _image_features(clip_model, pixel_values):
-    """HIP CLIP-L encode with weights packed from the HF module's state.  The packed bf16 copy is cached on the module,
-    keyed on (data_ptr, _version) of EVERY vision-tower tensor and the device: load_state_dict / an in-place update /
-    .to(device) rebuild it.  (Writes through `p.data` are invisible to any key: call `invalidate_packed_clip(model)`.)"""
+def _packed_clip(clip_model) -> "ops.ClipVitWeights":
+    """The HF module's vision tower packed for the HIP encoder.  The packed bf16 copy is cached on the module, keyed on
+    (data_ptr, _version) of EVERY vision-tower tensor and the device: load_state_dict / an in-place update / .to(device) rebuild
+    it.  (Writes through `p.data` are invisible to any key: call `invalidate_packed_clip(model)`.)"""
     packed = getattr(clip_model, "_tspo_packed", None)
     vm = clip_model.vision_model
     tensors = list(vm.parameters()) + [clip_model.visual_projection.weight]
@@ -265,7 +265,16 @@ def _image_features(clip_model, pixel_values):
         state["visual_projection.weight"] = clip_model.visual_projection.weight
         packed = (key, ops.ClipVitWeights(state, c, key[0]))
         clip_model._tspo_packed = packed
-    return ops.clip_vit_forward(packed[1], pixel_values)
+    return packed[1]
+
+
+def _image_features(clip_model, pixel_values, encode_chunk_frames=None):
+    """HIP CLIP-L encode with weights packed from the HF module's state (`_packed_clip`).  encode_chunk_frames = None: one call
+    over all frames; an int: in chunks of at most that many frames, workspace bounded by the largest chunk
+    (ops.clip_vit_forward_chunked)."""
+    if encode_chunk_frames is None:
+        return ops.clip_vit_forward(_packed_clip(clip_model), pixel_values)
+    return ops.clip_vit_forward_chunked(_packed_clip(clip_model), pixel_values, int(encode_chunk_frames))
 
 
 def invalidate_packed_clip(clip_model) -> None:
@@ -295,11 +304,11 @@ def _frames_to_pil(candidates, processor_type):
     return image_list
 
 
-def _frames_to_device_u8(candidates, processor_type, dev, clip_processor):
-    """uint8 frames -> GPU -> Pillow-exact resize/crop in HIP (tspo_preprocess_frames) -> uint8 [T,3,224,224]; the
-    normalisation is fused into the encoder's patch gather.  Returns None when the processor is not configured like
-    CLIP's default one or the frames are not a uniform uint8 batch (then the PIL path of the reference is used)."""
-    from .preprocess import preprocess_frames, processor_is_default_clip
+def _frames_as_u8(candidates, processor_type, clip_processor):
+    """The frames as ONE uint8 tensor [T,H,W,3] ('llava') / [T,3,H,W] wherever they live (no copy of a numpy array or a tensor),
+    or None when the processor is not configured like CLIP's default one or the frames are not a uniform uint8 batch (then the
+    PIL path of the reference is used)."""
+    from .preprocess import processor_is_default_clip
     ip = getattr(clip_processor, "image_processor", None)
     if ip is None or not processor_is_default_clip(ip):
         return None
@@ -311,31 +320,84 @@ def _frames_to_device_u8(candidates, processor_type, dev, clip_processor):
             arr = arr.to(torch.uint8) if arr.dtype != torch.uint8 else arr
         if arr.dtype != torch.uint8 or arr.ndim != 4:
             return None
+        return arr
+    except (ValueError, TypeError, RuntimeError):
+        return None
+
+
+def _frames_to_device_u8(candidates, processor_type, dev, clip_processor):
+    """uint8 frames -> GPU -> Pillow-exact resize/crop in HIP (tspo_preprocess_frames) -> uint8 [T,3,224,224]; the
+    normalisation is fused into the encoder's patch gather.  Returns None where `_frames_as_u8` does."""
+    from .preprocess import preprocess_frames
+    arr = _frames_as_u8(candidates, processor_type, clip_processor)
+    if arr is None:
+        return None
+    try:
         return preprocess_frames(arr.to(dev))
     except (ValueError, TypeError, RuntimeError):
         return None
 
 
+def _warn_pil_fallback():
+    global _PIL_FALLBACK_WARNED
+    if not _PIL_FALLBACK_WARNED:      # said once per process: the caller has lost the on-device front end (VERDICT r5 weak #9)
+        _PIL_FALLBACK_WARNED = True
+        import warnings
+        warnings.warn("tspo_amd: frames are preprocessed on the CPU by the stock CLIP processor (PIL, one frame at a time, as "
+                      "the reference does) - the on-device resize / crop (tspo_preprocess_frames) applies only to uniform uint8 "
+                      "frame batches and a processor configured like CLIP's default one; results are unchanged, the front end is "
+                      "~100x slower", RuntimeWarning, stacklevel=3)
+
+
+def _image_features_chunked_from_frames(clip_model, clip_processor, candidates, processor_type, dev, chunk_frames):
+    """encode_chunk_frames set: raw frames -> features [T, proj] without the whole video's raw frames, pixel_values or encoder
+    workspace ever being on the device.  Uniform uint8 frames stream from where they are (preprocess.encode_frames_streamed);
+    anything else runs the stock processor (PIL) and the encoder chunk by chunk of the same plan."""
+    from .preprocess import encode_frames_streamed
+    w = _packed_clip(clip_model)
+    T = len(candidates)
+    plan = ops.clip_chunk_plan(w, T, chunk_frames)      # ValueError (no plan for this chunk_frames) is the caller's to see
+    arr = _frames_as_u8(candidates, processor_type, clip_processor)
+    if arr is not None:
+        try:
+            return encode_frames_streamed(w, arr, chunk_frames)
+        except (ValueError, TypeError):          # a frame shape the preprocessing kernels do not take: the PIL path below
+            pass
+    _warn_pil_fallback()
+    feats = torch.empty((T, w.cfg["proj"]), dtype=torch.float32, device=dev)
+    lo = 0
+    for n in plan:
+        image_list = _frames_to_pil(candidates[lo:lo + n], processor_type)
+        px = clip_processor(images=image_list, return_tensors="pt", padding=True).to(dev)["pixel_values"]
+        ops.clip_vit_forward(w, px, out=feats[lo:lo + n])
+        lo += n
+    return feats
+
+
 _PIL_FALLBACK_WARNED = False
 
 
-def extract_clip_features_impl(clip_model, clip_processor, candidates, problem, processor_type='llava'):
+def extract_clip_features_impl(clip_model, clip_processor, candidates, problem, processor_type='llava',
+                               encode_chunk_frames=None):
     """temporal_agent.py:151-169 / utils.py:18-35 / tspo_trainer.py:387-404: text tower on stock
-    PyTorch-ROCm, all T frames through the HIP CLIP encoder, cosine clip score in HIP."""
+    PyTorch-ROCm, all T frames through the HIP CLIP encoder, cosine clip score in HIP.
+    encode_chunk_frames (default None = every frame in one encode, as the reference does): an int bounds the device memory of
+    the encode to chunks of at most that many frames - host frames are streamed to the device chunk by chunk while the previous
+    chunk encodes (INTEGRATION.md "Long videos"); the clip scores are still one call over all T features."""
     dev = next(clip_model.parameters()).device
     inputs_text = clip_processor(text=problem, return_tensors="pt", padding=True, truncation=True).to(dev)
     with torch.no_grad():
         text_features = _pooled(clip_model.get_text_features(**inputs_text))
+    if encode_chunk_frames is not None:
+        with torch.no_grad():
+            image_features = _image_features_chunked_from_frames(clip_model, clip_processor, candidates, processor_type, dev,
+                                                                 int(encode_chunk_frames))
+            clip_scores = ops.clip_scores(text_features[:1].float().unsqueeze(0), image_features.unsqueeze(0))[0]
+        dt = clip_model.dtype
+        return image_features.to(dt), text_features, clip_scores.to(dt)
     pixels = _frames_to_device_u8(candidates, processor_type, dev, clip_processor)
     if pixels is None:   # non-default processor config / ragged frames: the reference's own CPU PIL path
-        global _PIL_FALLBACK_WARNED
-        if not _PIL_FALLBACK_WARNED:      # said once per process: the caller has lost the on-device front end (VERDICT r5 weak #9)
-            _PIL_FALLBACK_WARNED = True
-            import warnings
-            warnings.warn("tspo_amd: frames are preprocessed on the CPU by the stock CLIP processor (PIL, one frame at a time, as "
-                          "the reference does) - the on-device resize / crop (tspo_preprocess_frames) applies only to uniform uint8 "
-                          "frame batches and a processor configured like CLIP's default one; results are unchanged, the front end is "
-                          "~100x slower", RuntimeWarning, stacklevel=2)
+        _warn_pil_fallback()
         image_list = _frames_to_pil(candidates, processor_type)
         pixels = clip_processor(images=image_list, return_tensors="pt", padding=True).to(dev)["pixel_values"]
     with torch.no_grad():
@@ -354,17 +416,23 @@ except Exception:  # pragma: no cover
 class TSPOModel(CLIPModel):
     """CLIP-L + selector ("TSPO-0.4B"), reference API (temporal_agent.py:146-231)."""
 
+    # Long videos (not a constructor argument: the reference's signature stays): None = every frame of a video in ONE encode, as
+    # the reference does (~5 MB of workspace per CLIP-L/14 frame); an int = encode in chunks of at most that many frames - bounded
+    # device memory, host frames streamed chunk by chunk (extract_clip_features_impl; INTEGRATION.md "Long videos").
+    encode_chunk_frames = None
+
     def __init__(self, clip_config):
         super().__init__(clip_config)
         self.selector = MultiModal_Align()
 
     def extract_feature(self, clip_processor, candidates, problem, processor_type='llava'):
-        return extract_clip_features_impl(self, clip_processor, candidates, problem, processor_type)
+        return extract_clip_features_impl(self, clip_processor, candidates, problem, processor_type,
+                                          encode_chunk_frames=self.encode_chunk_frames)
 
     def extract_feature_from_pixels(self, pixel_values, text_features):
         """Fast path for already-preprocessed frames [T,3,224,224] (any of f32/bf16/f16/uint8) on the GPU."""
         with torch.no_grad():
-            image_features = _image_features(self, pixel_values)
+            image_features = _image_features(self, pixel_values, self.encode_chunk_frames)
             clip_scores = ops.clip_scores(text_features[:1].float().unsqueeze(0), image_features.unsqueeze(0))[0]
         return image_features, text_features, clip_scores
 
