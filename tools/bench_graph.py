@@ -1,6 +1,7 @@
 """The scoring step (configs[1]: 1024 frames -> indices) eager vs replayed as ONE captured graph (torch.cuda.CUDAGraph = hipGraph), same
 box, alternating: the whole path is capturable (every launch on the current stream, no host synchronisation, no allocation by the
 library) - and replay changes nothing (+-0.1 %, round 5): the step is GPU-bound, its ~220 launches leave no gaps to close.
+This tool times and prints; that a captured step replays bit for bit is asserted by tests/test_gpu_contract.py (test_graph_frame_scorer_call).
     python tools/bench_graph.py"""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
