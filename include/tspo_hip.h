@@ -248,6 +248,59 @@ int tspo_policy_backward_ex(const tspo_selector_weights* w, const float* img, co
                             float* norm_partials, int* n_partials);
 
 /* ------------------------------------------------------------------------
+ * Videos of different lengths in one padded batch (the `_len` entries)
+ * ------------------------------------------------------------------------
+ * The policy step over B videos of DIFFERENT lengths as one dense batch: every tensor keeps its shape, T is the padded length
+ * (the longest video) and stays the row stride, the workspace size and the grid size; `lengths` (int32 [B], DEVICE memory,
+ * 1 <= lengths[b] <= T) says how many leading rows of video b are real.  Rows t >= lengths[b] are padding.  Each entry is its
+ * `_ex` form (tspo_grpo_pg_grad: its plain form) followed by `lengths, min_length`; lengths == NULL is exactly that form, bit
+ * for bit.  A caller discovers the capability by symbol lookup (the ABI version is unchanged).
+ *
+ * `lengths` lives on the device so that nothing synchronises and the step stays capturable in a graph; the library cannot
+ * validate device values, so the caller vouches for a host lower bound `min_length` (1 <= min_length <= T, else TSPO_EINVAL;
+ * the sampler also needs k <= min_length, else TSPO_EINVAL before any device work) and every kernel uses
+ *   L_b = min(max(lengths[b], min_length), T):
+ * whatever the buffer holds, no kernel reads or writes outside its row and no rollout selects fewer than k frames.
+ *
+ * Video b is computed as if it were alone with T = L_b:
+ *   forward   position t / L_b; band keys {clamp(t - w/2 + i, 0, L_b - 1)}; scores[b, t >= L_b] = -inf;
+ *   sampler   the row is [0, L_b): Philox counter (t, g, b), offset and prompts_per_offset rule unchanged, logp a log-softmax
+ *             over L_b entries with -inf padding, probs / noise_out padding 0, every index < L_b;
+ *   backward  dL/dscores and the dh2 row of a padding frame are exactly 0.
+ * Padding never leaks: the GEMMs are unchanged and run over all B*T rows, and every buffer one of them (or a column sum) reads
+ * gets its padding rows written by the same call - exact zeros in the gradient buffers dh2, dh1, dctx, dqkv, zeros in the saved
+ * activations x_pe and ctx - so a padding row adds exact zeros to every weight and bias gradient in all three precisions.  The
+ * softmax weights and their gradients of padding queries are never read.  Padding rows of img and clip must be FINITE (the
+ * residual add of mlp.2 reads img); they influence no valid output row and no gradient.  Padding rows of temporal_attn are
+ * unspecified.  The workspace is the one of the padded dims (tspo_selector_workspace_bytes(B, T, ..)); a backward needs the
+ * workspace of a forward with the same lengths.                                                                             */
+int tspo_gumbel_topk_len(const float* logits, const float* noise, uint64_t seed, uint64_t offset,
+                         int B, int G, int T, int k, float tau,
+                         int64_t* idx, float* logp, float* probs, float* noise_out,
+                         tspo_stream_t stream, int prompts_per_offset, const int32_t* lengths, int min_length);
+int tspo_grpo_pg_grad_len(const float* rewards, const float* logp, const int64_t* idx,
+                          int B, int G, int T, int k, float eps, float scale,
+                          float* adv, float* dlogits, float* loss, tspo_stream_t stream,
+                          const int32_t* lengths, int min_length);
+int tspo_selector_forward_len(const tspo_selector_weights* w, const float* img, const float* txt, const float* clip,
+                              int B, int T, int D, int H, int M, int window, float tau,
+                              float* scores, float* temporal_attn,
+                              void* workspace, size_t workspace_bytes, tspo_stream_t stream, int flags,
+                              const int32_t* lengths, int min_length);
+int tspo_selector_backward_len(const tspo_selector_weights* w, const float* img, const float* txt,
+                               const float* dscores, int B, int T, int D, int H, int M, int window, float tau,
+                               const tspo_selector_grads* grads,
+                               void* workspace, size_t workspace_bytes, tspo_stream_t stream, int flags,
+                               const int32_t* lengths, int min_length);
+int tspo_policy_backward_len(const tspo_selector_weights* w, const float* img, const float* txt,
+                             const float* rewards, const float* logp, const int64_t* idx,
+                             int B, int T, int D, int H, int M, int window, float tau,
+                             int G, int k, float adv_eps, float scale,
+                             const tspo_selector_grads* grads, float* adv, float* loss,
+                             void* workspace, size_t workspace_bytes, tspo_stream_t stream, int flags,
+                             float* norm_partials, int* n_partials, const int32_t* lengths, int min_length);
+
+/* ------------------------------------------------------------------------
  * Optimiser on the flat parameter bucket
  * ------------------------------------------------------------------------ */
 

@@ -66,6 +66,16 @@ SIGNATURES = {
                                   C.POINTER(SelectorGrads), _p, _p, _p, _sz, _p, _i]),
     "tspo_policy_backward_ex": (_i, [C.POINTER(SelectorWeights), _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _i, _i, _f, _f,
                                      C.POINTER(SelectorGrads), _p, _p, _p, _sz, _p, _i, _p, C.POINTER(C.c_int)]),
+    # the `_len` entries: the `_ex` signature + (lengths int32 [B] on the device, host min_length) - videos of different lengths in
+    # one padded batch
+    "tspo_gumbel_topk_len": (_i, [_p, _p, _u64, _u64, _i, _i, _i, _i, _f, _p, _p, _p, _p, _p, _i, _p, _i]),
+    "tspo_grpo_pg_grad_len": (_i, [_p, _p, _p, _i, _i, _i, _i, _f, _f, _p, _p, _p, _p, _p, _i]),
+    "tspo_selector_forward_len": (_i, [C.POINTER(SelectorWeights), _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _p, _p, _p, _sz, _p, _i,
+                                       _p, _i]),
+    "tspo_selector_backward_len": (_i, [C.POINTER(SelectorWeights), _p, _p, _p, _i, _i, _i, _i, _i, _i, _f,
+                                        C.POINTER(SelectorGrads), _p, _sz, _p, _i, _p, _i]),
+    "tspo_policy_backward_len": (_i, [C.POINTER(SelectorWeights), _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _i, _i, _f, _f,
+                                      C.POINTER(SelectorGrads), _p, _p, _p, _sz, _p, _i, _p, C.POINTER(C.c_int), _p, _i]),
     "tspo_selector_supported_flags": (_i, [_i]),
     "tspo_grad_norm_scale": (_i, [_p, _sz, _f, _f, _p, _p, _sz, _p]),
     "tspo_adamw_step": (_i, [_p, _p, _p, _p, _sz, _f, _f, _f, _f, _f, _i, _f, _p, _p]),

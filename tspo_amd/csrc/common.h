@@ -56,6 +56,12 @@ __device__ __forceinline__ int wave_sum_i(int v) {
   return v;
 }
 
+// Per-video length of a padded batch (rows t >= L_b of a [B, T, ..] tensor are padding).  lengths == nullptr: T.  A device value is
+// clamped to [min_length, T], so no kernel leaves its row and no sampler sees fewer than min_length frames whatever the buffer holds.
+__device__ __forceinline__ int row_length(const int32_t* __restrict__ lengths, int min_length, int b, int T) {
+  return lengths ? min(max(lengths[b], min_length), T) : T;
+}
+
 // Block-wide reductions through a small LDS scratch (>= 32 floats). All threads get the result.
 __device__ __forceinline__ float block_sum(float v, float* scratch) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;

@@ -240,16 +240,20 @@ extern "C" int tspo_binmax(const float* scores, int B, int T, int k, int64_t* id
 // Gumbel-top-k for all (prompt, rollout) pairs in one launch.  LONG (T > SEL_LDS_KEYS): the row does not fit in LDS, so the
 // perturbed logit z(t) - a pure function of (logit, injected noise or the Philox counter) - is recomputed on each of the
 // selection's passes, like the global-key path of topk_sorted_kernel; results are identical to the LDS-resident form.
+// `lengths` (nullable): the row of prompt b is its first L_b = row_length(..) entries (T_row stays the stride and the LDS layout): the
+// selection, both softmaxes and the Philox counters are those of a call with T = L_b; outputs past L_b are padding (logp -inf, probs
+// and noise_out 0).
 template <bool LONG>
 __global__ __launch_bounds__(SEL_THREADS) void gumbel_topk_kernel(
     const float* __restrict__ logits, const float* __restrict__ noise, uint32_t key0, uint32_t seed_hi, uint64_t offset,
-    int per_offset, int G, int T, int k, float tau, int64_t* __restrict__ idx, float* __restrict__ logp,
-    float* __restrict__ probs, float* __restrict__ noise_out) {
-  extern __shared__ __attribute__((aligned(16))) uint32_t lds_keys[];  // T keys, then T floats (z) when probs wanted
+    int per_offset, int G, int T_row, int k, float tau, int64_t* __restrict__ idx, float* __restrict__ logp,
+    float* __restrict__ probs, float* __restrict__ noise_out, const int32_t* __restrict__ lengths, int min_length) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t lds_keys[];  // T_row keys, then T_row floats (z) when probs wanted
   __shared__ SelShared sh;
   __shared__ float red[32];
   const int g = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-  const float* l = logits + (size_t)b * T;
+  const float* l = logits + (size_t)b * T_row;
+  const int T = row_length(lengths, min_length, b, T_row);   // block-uniform
   if (g == G) {   // the extra workgroup of prompt b: log(softmax(logits)) - no noise (model/utils.py:78).  Its own workgroup since
                   // round 5 (rollout 0's workgroup did it after its selection: the longest chain of the launch, 8.8 -> 7 us)
     float lmax = -INFINITY;
@@ -258,11 +262,12 @@ __global__ __launch_bounds__(SEL_THREADS) void gumbel_topk_kernel(
     float se = 0.f;
     for (int t = tid; t < T; t += SEL_THREADS) se += expf(l[t] - lmax);
     se = block_sum(se, red);
-    for (int t = tid; t < T; t += SEL_THREADS) logp[(size_t)b * T + t] = logf(expf(l[t] - lmax) / se);
+    for (int t = tid; t < T; t += SEL_THREADS) logp[(size_t)b * T_row + t] = logf(expf(l[t] - lmax) / se);
+    for (int t = T + tid; t < T_row; t += SEL_THREADS) logp[(size_t)b * T_row + t] = -INFINITY;
     return;
   }
-  const size_t row = ((size_t)b * G + g) * T;
-  float* zbuf = reinterpret_cast<float*>(lds_keys + (LONG ? 0 : T));
+  const size_t row = ((size_t)b * G + g) * T_row;
+  float* zbuf = reinterpret_cast<float*>(lds_keys + (LONG ? 0 : T_row));
   // per_offset = p > 0: prompts come in groups of p that would have been separate calls (micro-steps of one optimizer step):
   // prompt b draws what prompt b % p of a call with offset + b / p draws
   const uint64_t off = per_offset > 0 ? offset + (uint64_t)(b / per_offset) : offset;
@@ -282,6 +287,10 @@ __global__ __launch_bounds__(SEL_THREADS) void gumbel_topk_kernel(
       if (probs) zbuf[t] = z;
     }
     zmax = fmaxf(zmax, z);
+  }
+  for (int t = T + tid; t < T_row; t += SEL_THREADS) {
+    if (noise_out) noise_out[row + t] = 0.f;
+    if (probs) probs[row + t] = 0.f;
   }
   __syncthreads();
   if (LONG) {
@@ -313,12 +322,14 @@ __global__ __launch_bounds__(SEL_THREADS) void gumbel_topk_kernel(
   }
 }
 
-extern "C" int tspo_gumbel_topk_ex(const float* logits, const float* noise, uint64_t seed, uint64_t offset, int B, int G,
-                                   int T, int k, float tau, int64_t* idx, float* logp, float* probs, float* noise_out,
-                                   tspo_stream_t stream, int prompts_per_offset) {
+static int gumbel_topk_impl(const float* logits, const float* noise, uint64_t seed, uint64_t offset, int B, int G,
+                            int T, int k, float tau, int64_t* idx, float* logp, float* probs, float* noise_out,
+                            tspo_stream_t stream, int prompts_per_offset, const int32_t* lengths, int min_length) {
   TSPO_REQUIRE(logits && idx, "gumbel_topk: null pointer");
   TSPO_REQUIRE(B >= 0 && G >= 1 && T >= 1 && k >= 1, "gumbel_topk: bad dims B=%d G=%d T=%d k=%d", B, G, T, k);
   TSPO_REQUIRE(k <= T, "gumbel_topk: selected index k out of range (k=%d > T=%d)", k, T);
+  TSPO_REQUIRE(!lengths || (min_length >= 1 && min_length <= T), "gumbel_topk: min_length=%d must be in [1, T=%d]", min_length, T);
+  TSPO_REQUIRE(!lengths || k <= min_length, "gumbel_topk: selected index k out of range (k=%d > min_length=%d)", k, min_length);
   TSPO_REQUIRE(tau > 0.f, "gumbel_topk: tau must be > 0");
   TSPO_REQUIRE(prompts_per_offset >= 0 && (prompts_per_offset == 0 || B % prompts_per_offset == 0),
                "gumbel_topk: prompts_per_offset=%d does not divide B=%d", prompts_per_offset, B);
@@ -327,12 +338,25 @@ extern "C" int tspo_gumbel_topk_ex(const float* logits, const float* noise, uint
   if (T <= SEL_LDS_KEYS) {
     const size_t lds = (size_t)T * 4 * (probs ? 2 : 1);
     hipLaunchKernelGGL(gumbel_topk_kernel<false>, dim3(G + (logp ? 1 : 0), B), dim3(SEL_THREADS), lds, (hipStream_t)stream, logits, noise, key0,
-                       seed_hi, offset, prompts_per_offset, G, T, k, tau, idx, logp, probs, noise_out);
+                       seed_hi, offset, prompts_per_offset, G, T, k, tau, idx, logp, probs, noise_out, lengths, min_length);
   } else {
     hipLaunchKernelGGL(gumbel_topk_kernel<true>, dim3(G + (logp ? 1 : 0), B), dim3(SEL_THREADS), 0, (hipStream_t)stream, logits, noise, key0,
-                       seed_hi, offset, prompts_per_offset, G, T, k, tau, idx, logp, probs, noise_out);
+                       seed_hi, offset, prompts_per_offset, G, T, k, tau, idx, logp, probs, noise_out, lengths, min_length);
   }
   return tspo::check_launch("gumbel_topk");
+}
+
+extern "C" int tspo_gumbel_topk_ex(const float* logits, const float* noise, uint64_t seed, uint64_t offset, int B, int G,
+                                   int T, int k, float tau, int64_t* idx, float* logp, float* probs, float* noise_out,
+                                   tspo_stream_t stream, int prompts_per_offset) {
+  return gumbel_topk_impl(logits, noise, seed, offset, B, G, T, k, tau, idx, logp, probs, noise_out, stream, prompts_per_offset,
+                          nullptr, 0);
+}
+extern "C" int tspo_gumbel_topk_len(const float* logits, const float* noise, uint64_t seed, uint64_t offset, int B, int G,
+                                    int T, int k, float tau, int64_t* idx, float* logp, float* probs, float* noise_out,
+                                    tspo_stream_t stream, int prompts_per_offset, const int32_t* lengths, int min_length) {
+  return gumbel_topk_impl(logits, noise, seed, offset, B, G, T, k, tau, idx, logp, probs, noise_out, stream, prompts_per_offset,
+                          lengths, min_length);
 }
 
 extern "C" int tspo_gumbel_topk(const float* logits, const float* noise, uint64_t seed, uint64_t offset, int B, int G,
@@ -418,7 +442,8 @@ extern "C" int tspo_pg_grad_logits(const float* logp, const int64_t* idx, const 
 __global__ __launch_bounds__(256) void grpo_pg_grad_kernel(const float* __restrict__ rewards, const float* __restrict__ logp,
                                                            const int64_t* __restrict__ idx, int G, int T, int k, float eps,
                                                            float scale, float* __restrict__ adv_out,
-                                                           float* __restrict__ dlogits, float* __restrict__ loss) {
+                                                           float* __restrict__ dlogits, float* __restrict__ loss,
+                                                           const int32_t* __restrict__ lengths, int min_length) {
   extern __shared__ __attribute__((aligned(16))) int lds_idx[];  // G*k ints then G floats
   float* a = reinterpret_cast<float*>(lds_idx + (size_t)G * k);
   const int b = blockIdx.x, tid = threadIdx.x;   // blockIdx.y: 256-frame slice of the row
@@ -457,21 +482,33 @@ __global__ __launch_bounds__(256) void grpo_pg_grad_kernel(const float* __restri
       }
       acc += a[g] * ((hit ? invk : 0.f) - p);
     }
-    dlogits[(size_t)b * T + t] = -invG * acc * scale;
+    // a padding frame (t >= L_b, `lengths`) is in no rollout and has probability 0: exactly 0, whatever its logp holds
+    dlogits[(size_t)b * T + t] = t < row_length(lengths, min_length, b, T) ? -invG * acc * scale : 0.f;
   }
   if (loss && tid == 0 && blockIdx.y == 0) loss[b] = -sumA * invG;
 }
 
-extern "C" int tspo_grpo_pg_grad(const float* rewards, const float* logp, const int64_t* idx, int B, int G, int T, int k,
-                                 float eps, float scale, float* adv, float* dlogits, float* loss, tspo_stream_t stream) {
+static int grpo_pg_grad_impl(const float* rewards, const float* logp, const int64_t* idx, int B, int G, int T, int k,
+                                 float eps, float scale, float* adv, float* dlogits, float* loss, tspo_stream_t stream,
+                                 const int32_t* lengths, int min_length) {
   TSPO_REQUIRE(rewards && logp && idx && adv && dlogits, "grpo_pg_grad: null pointer");
   TSPO_REQUIRE(B >= 0 && G >= 1 && T >= 1 && k >= 1 && k <= T, "grpo_pg_grad: bad dims B=%d G=%d T=%d k=%d", B, G, T, k);
+  TSPO_REQUIRE(!lengths || (min_length >= 1 && min_length <= T), "grpo_pg_grad: min_length=%d must be in [1, T=%d]", min_length, T);
   const size_t lds = (size_t)G * k * 4 + (size_t)G * 4;
   TSPO_REQUIRE(lds <= 64 * 1024, "grpo_pg_grad: G*k=%d too large for LDS", G * k);
   if (B == 0) return TSPO_OK;
   hipLaunchKernelGGL(grpo_pg_grad_kernel, dim3(B, (T + 255) / 256), dim3(256), lds, (hipStream_t)stream, rewards, logp, idx, G,
-                     T, k, eps, scale, adv, dlogits, loss);
+                     T, k, eps, scale, adv, dlogits, loss, lengths, min_length);
   return tspo::check_launch("grpo_pg_grad");
+}
+extern "C" int tspo_grpo_pg_grad(const float* rewards, const float* logp, const int64_t* idx, int B, int G, int T, int k,
+                                 float eps, float scale, float* adv, float* dlogits, float* loss, tspo_stream_t stream) {
+  return grpo_pg_grad_impl(rewards, logp, idx, B, G, T, k, eps, scale, adv, dlogits, loss, stream, nullptr, 0);
+}
+extern "C" int tspo_grpo_pg_grad_len(const float* rewards, const float* logp, const int64_t* idx, int B, int G, int T, int k,
+                                     float eps, float scale, float* adv, float* dlogits, float* loss, tspo_stream_t stream,
+                                     const int32_t* lengths, int min_length) {
+  return grpo_pg_grad_impl(rewards, logp, idx, B, G, T, k, eps, scale, adv, dlogits, loss, stream, lengths, min_length);
 }
 
 // ---------------------------------------------------------------------------

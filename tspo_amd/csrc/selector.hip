@@ -66,8 +66,11 @@ __device__ __forceinline__ f32x4 bf_mfma(const BfOp<P>& a, const BfOp<P>& b, f32
 // ---------------------------------------------------------------------------
 // x_pe = x + pe, pe[t,2i] = sin((t/T) * exp(2i * -ln(1e4)/C)), pe[t,2i+1] = cos(..)
 // (model/temporal_agent.py:10-19, 128-129); all fp32 like torch.
+// `lengths` (nullable, every kernel below that takes it): video b has L_b = row_length(..) <= T frames and is computed as if it
+// were alone with T = L_b; T stays the row stride.  Rows t >= L_b are padding: zeros here.
 __global__ __launch_bounds__(256) void posenc_add_kernel(const float* __restrict__ x, float* __restrict__ out,
-                                                         int T, int D, size_t total) {
+                                                         int T, int D, size_t total, const int32_t* __restrict__ lengths,
+                                                         int min_length) {
   // one thread per (row, channel pair): the pair (2i, 2i+1) shares its angle - one expf and one sincosf for two outputs
   // (same values as separate sinf / cosf calls), 8-byte loads and stores.  D is even (D % 64 == 0).
   const float c = -9.21034049987793f / (float)D;
@@ -76,8 +79,13 @@ __global__ __launch_bounds__(256) void posenc_add_kernel(const float* __restrict
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < pairs; i += (size_t)gridDim.x * 256) {
     const int pi = (int)(i % hd);
     const int t = (int)((i / hd) % T);
+    const int L = row_length(lengths, min_length, (int)(i / hd / T), T);
+    if (t >= L) {   // padding row: x_pe is an operand of the q|k|v weight gradient, which runs over all B*T rows
+      reinterpret_cast<float2*>(out)[i] = make_float2(0.f, 0.f);
+      continue;
+    }
     const float div = expf((float)(2 * pi) * c);
-    const float pos = (float)t / (float)T;
+    const float pos = (float)t / (float)L;
     const float a = pos * div;
     float sn, cs;
     sincosf(a, &sn, &cs);
@@ -342,7 +350,8 @@ __device__ __forceinline__ float half_max(float v) {
 }
 
 __global__ __launch_bounds__(256) void band_attn_fwd_kernel(const float* __restrict__ qkv, float* __restrict__ ctx,
-                                                            float* __restrict__ P, int B, int T, int D, int H, int w) {
+                                                            float* __restrict__ P, int B, int T, int D, int H, int w,
+                                                            const int32_t* __restrict__ lengths, int min_length) {
   const int hl = threadIdx.x & 31;
   const long pair = (long)blockIdx.x * 8 + (threadIdx.x >> 5);
   if (pair >= (long)B * T * H) return;
@@ -351,8 +360,17 @@ __global__ __launch_bounds__(256) void band_attn_fwd_kernel(const float* __restr
   const int t = (int)(row % T);
   const long rowb = row - t;  // first row of this video
   const int hd = D / H;
+  const int L = row_length(lengths, min_length, (int)(row / T), T);
+  if (t >= L) {   // padding row: ctx is an operand of the mlp.0 weight gradient (P of a padding query is never read)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const int e = hl + 32 * c;
+      if (e < hd) ctx[row * D + h * hd + e] = 0.f;
+    }
+    return;
+  }
   const float scale = 1.0f / sqrtf((float)hd);
-  const int lo = max(0, t - w / 2), hi = min(T - 1, t - w / 2 + w - 1);
+  const int lo = max(0, t - w / 2), hi = min(L - 1, t - w / 2 + w - 1);
   const int n = hi - lo + 1;
   const size_t ld = (size_t)3 * D;
   float qv[4];
@@ -423,7 +441,8 @@ __global__ __launch_bounds__(256) void band_attn_bwd_q_kernel(const float* __res
                                                               const float* __restrict__ P,
                                                               const float* __restrict__ dctx,
                                                               float* __restrict__ dqkv, float* __restrict__ dS, int B,
-                                                              int T, int D, int H, int w) {
+                                                              int T, int D, int H, int w,
+                                                              const int32_t* __restrict__ lengths, int min_length) {
   const int hl = threadIdx.x & 31;
   const long pair = (long)blockIdx.x * 8 + (threadIdx.x >> 5);
   if (pair >= (long)B * T * H) return;
@@ -432,10 +451,19 @@ __global__ __launch_bounds__(256) void band_attn_bwd_q_kernel(const float* __res
   const int t = (int)(row % T);
   const long rowb = row - t;
   const int hd = D / H;
-  const float scale = 1.0f / sqrtf((float)hd);
-  const int lo = max(0, t - w / 2), hi = min(T - 1, t - w / 2 + w - 1);
-  const int n = hi - lo + 1;
   const size_t ld = (size_t)3 * D;
+  const int L = row_length(lengths, min_length, (int)(row / T), T);
+  if (t >= L) {   // padding row: dq = 0 (dqkv is an operand of the q|k|v weight and bias gradients; dS of a padding query is never read)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const int e = hl + 32 * c;
+      if (e < hd) dqkv[row * ld + h * hd + e] = 0.f;
+    }
+    return;
+  }
+  const float scale = 1.0f / sqrtf((float)hd);
+  const int lo = max(0, t - w / 2), hi = min(L - 1, t - w / 2 + w - 1);
+  const int n = hi - lo + 1;
   float dc[4];
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
@@ -484,7 +512,7 @@ __global__ __launch_bounds__(256) void band_attn_bwd_kv_kernel(const float* __re
                                                                const float* __restrict__ dS,
                                                                const float* __restrict__ dctx,
                                                                float* __restrict__ dqkv, int B, int T, int D, int H,
-                                                               int w) {
+                                                               int w, const int32_t* __restrict__ lengths, int min_length) {
   const int hl = threadIdx.x & 31;
   const long pair = (long)blockIdx.x * 8 + (threadIdx.x >> 5);
   if (pair >= (long)B * T * H) return;
@@ -494,8 +522,9 @@ __global__ __launch_bounds__(256) void band_attn_bwd_kv_kernel(const float* __re
   const long rowb = row - j;
   const int hd = D / H;
   const size_t ld = (size_t)3 * D;
-  // queries t with j in [max(0,t-w/2), min(T-1,t-w/2+w-1)]  <=>  j-(w-1-w/2) <= t <= j+w/2
-  const int tlo = max(0, j - (w - 1 - w / 2)), thi = min(T - 1, j + w / 2);
+  const int L = row_length(lengths, min_length, (int)(row / T), T);
+  // queries t with j in [max(0,t-w/2), min(L-1,t-w/2+w-1)]  <=>  j-(w-1-w/2) <= t <= j+w/2; a padding key (j >= L) has none: dk = dv = 0
+  const int tlo = max(0, j - (w - 1 - w / 2)), thi = j < L ? min(L - 1, j + w / 2) : -1;
   float dk[4] = {0.f, 0.f, 0.f, 0.f}, dv[4] = {0.f, 0.f, 0.f, 0.f};
   for (int t = tlo; t <= thi; ++t) {
     const int lo_t = max(0, t - w / 2);
@@ -620,9 +649,10 @@ __device__ __forceinline__ void band_rows_mma(const f32x4 (&coef)[2], const Band
     }
 }
 
-// store out (rows i0+4q+r of the block, head columns in the lane-vector grouping) to dst (head's first column, row 0)
+// store out (rows i0+4q+r of the block, head columns in the lane-vector grouping) to dst (head's first column, row 0); rows
+// L <= t < T (padding of a video shorter than the row stride) get zeros
 template <int HD>
-__device__ __forceinline__ void band_store_rows(const f32x4 (&out)[HD / 16], float* dst, size_t ld, int i0, int T, int q,
+__device__ __forceinline__ void band_store_rows(const f32x4 (&out)[HD / 16], float* dst, size_t ld, int i0, int L, int T, int q,
                                                 int l15) {
   using HC = HeadCols<HD>;
 #pragma unroll
@@ -633,12 +663,21 @@ __device__ __forceinline__ void band_store_rows(const f32x4 (&out)[HD / 16], flo
 #pragma unroll
       for (int g = 0; g < HC::N4; ++g) {
         const f32x4 v = {out[4 * g][r], out[4 * g + 1][r], out[4 * g + 2][r], out[4 * g + 3][r]};
-        *reinterpret_cast<f32x4*>(dr + 64 * g + 4 * l15) = v;
+        *reinterpret_cast<f32x4*>(dr + 64 * g + 4 * l15) = t < L ? v : (f32x4){0.f, 0.f, 0.f, 0.f};
       }
-      if (HC::HAS2) *reinterpret_cast<float2*>(dr + HC::BASE2 + 2 * l15) = make_float2(out[4 * HC::N4][r], out[4 * HC::N4 + 1][r]);
-      if (HC::HAS1) dr[HC::BASE1 + l15] = out[HC::TILES - 1][r];
+      if (HC::HAS2)
+        *reinterpret_cast<float2*>(dr + HC::BASE2 + 2 * l15) = t < L ? make_float2(out[4 * HC::N4][r], out[4 * HC::N4 + 1][r]) : make_float2(0.f, 0.f);
+      if (HC::HAS1) dr[HC::BASE1 + l15] = t < L ? out[HC::TILES - 1][r] : 0.f;
     }
   }
+}
+// a 16-row block that lies wholly in padding (i0 >= L): zeros
+template <int HD>
+__device__ __forceinline__ void band_zero_rows(float* dst, size_t ld, int i0, int T, int q, int l15) {
+  f32x4 z[HD / 16];
+#pragma unroll
+  for (int c = 0; c < HD / 16; ++c) z[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  band_store_rows<HD>(z, dst, ld, i0, 0, T, q, l15);
 }
 
 struct BandBlk {   // wave -> (video, head, 16-row block)
@@ -670,29 +709,35 @@ __device__ __forceinline__ float xor_max_hi(float v) {
 
 template <int HD>
 __global__ __launch_bounds__(256) void band_attn_fwd_mfma_kernel(const float* __restrict__ qkv, float* __restrict__ ctx,
-                                                                 float* __restrict__ P, int B, int T, int D, int H, int w) {
+                                                                 float* __restrict__ P, int B, int T, int D, int H, int w,
+                                                                 const int32_t* __restrict__ lengths, int min_length) {
   const BandBlk k = band_block(B, T, H);
   if (!k.live) return;
   const int lane = threadIdx.x & 63, l15 = lane & 15, q = lane >> 4;
   const size_t ld = (size_t)3 * D;
+  const int L = row_length(lengths, min_length, k.b, T);        // frames of this video (wave-uniform); T stays the row stride
+  if (k.i0 >= L) {   // padding rows: ctx is an operand of the mlp.0 weight gradient (P of a padding query is never read)
+    band_zero_rows<HD>(ctx + (size_t)k.b * T * D + k.h * HD, (size_t)D, k.i0, T, q, l15);
+    return;
+  }
   const float* base = qkv + (size_t)k.b * T * ld + k.h * HD;   // row 0 of the video, q columns of the head
   const int kb = k.i0 - w / 2;                                   // first key of the tile pair (may be < 0)
   const int t = k.i0 + l15;                                      // this lane's query (MFMA column)
-  const int tq = t < T ? t : T - 1;
+  const int tq = t < L ? t : L - 1;
   const float* arow[2];
 #pragma unroll
   for (int tt = 0; tt < 2; ++tt) {
     int kr = kb + 16 * tt + l15;
-    kr = kr < 0 ? 0 : (kr > T - 1 ? T - 1 : kr);
+    kr = kr < 0 ? 0 : (kr > L - 1 ? L - 1 : kr);
     arow[tt] = base + (size_t)kr * ld + D;
   }
   BandRows<HD> vrows;
-  band_rows_load<HD>(base + 2 * D, ld, kb, T, q, l15, vrows);   // the V rows of the second product, requested before the first
+  band_rows_load<HD>(base + 2 * D, ld, kb, L, q, l15, vrows);   // the V rows of the second product, requested before the first
   asm volatile("" ::: "memory");                                 // (keeps the requests here: hipcc sinks them behind the softmax)
   f32x4 sc[2];
   band_scores_T<HD>(arow, base + (size_t)tq * ld, q, sc);
   const float scale = 1.0f / sqrtf((float)HD);
-  const int lo = max(0, tq - w / 2), hi = min(T - 1, tq - w / 2 + w - 1);
+  const int lo = max(0, tq - w / 2), hi = min(L - 1, tq - w / 2 + w - 1);
   float m = -INFINITY;
   bool ok[2][4];
 #pragma unroll
@@ -721,11 +766,11 @@ __global__ __launch_bounds__(256) void band_attn_fwd_mfma_kernel(const float* __
     for (int r = 0; r < 4; ++r) {
       sc[tt][r] = sc[tt][r] / l;
       const int slot = kb + 16 * tt + 4 * q + r - lo;
-      if (t < T && slot >= 0 && slot < w) P[pair * w + slot] = sc[tt][r];   // slots past the clipped window hold 0
+      if (t < L && slot >= 0 && slot < w) P[pair * w + slot] = sc[tt][r];   // slots past the clipped window hold 0
     }
   f32x4 out[HD / 16];
   band_rows_mma<HD>(sc, vrows, out);
-  band_store_rows<HD>(out, ctx + (size_t)k.b * T * D + k.h * HD, (size_t)D, k.i0, T, q, l15);
+  band_store_rows<HD>(out, ctx + (size_t)k.b * T * D + k.h * HD, (size_t)D, k.i0, L, T, q, l15);
 }
 
 // backward part 1 (MFMA): dS (scaled) and dq for a block of 16 queries
@@ -733,27 +778,33 @@ template <int HD>
 __global__ __launch_bounds__(256) void band_attn_bwd_q_mfma_kernel(const float* __restrict__ qkv, const float* __restrict__ P,
                                                                    const float* __restrict__ dctx,
                                                                    float* __restrict__ dqkv, float* __restrict__ dS, int B,
-                                                                   int T, int D, int H, int w) {
+                                                                   int T, int D, int H, int w,
+                                                                   const int32_t* __restrict__ lengths, int min_length) {
   const BandBlk k = band_block(B, T, H);
   if (!k.live) return;
   const int lane = threadIdx.x & 63, l15 = lane & 15, q = lane >> 4;
   const size_t ld = (size_t)3 * D;
+  const int L = row_length(lengths, min_length, k.b, T);
+  if (k.i0 >= L) {   // padding rows: dq = 0 (dqkv is an operand of the q|k|v weight and bias gradients; their dS is never read)
+    band_zero_rows<HD>(dqkv + (size_t)k.b * T * ld + k.h * HD, ld, k.i0, T, q, l15);
+    return;
+  }
   const float* base = qkv + (size_t)k.b * T * ld + k.h * HD;
   const int kb = k.i0 - w / 2;
   const int t = k.i0 + l15;
-  const int tq = t < T ? t : T - 1;
+  const int tq = t < L ? t : L - 1;
   const float* arow[2];
 #pragma unroll
   for (int tt = 0; tt < 2; ++tt) {
     int kr = kb + 16 * tt + l15;
-    kr = kr < 0 ? 0 : (kr > T - 1 ? T - 1 : kr);
+    kr = kr < 0 ? 0 : (kr > L - 1 ? L - 1 : kr);
     arow[tt] = base + (size_t)kr * ld + 2 * D;   // V rows
   }
   BandRows<HD> krows;
-  band_rows_load<HD>(base + D, ld, kb, T, q, l15, krows);   // the K rows of dq = dS . K, requested before the first product
+  band_rows_load<HD>(base + D, ld, kb, L, q, l15, krows);   // the K rows of dq = dS . K, requested before the first product
   asm volatile("" ::: "memory");
   const float scale = 1.0f / sqrtf((float)HD);
-  const int lo = max(0, tq - w / 2), hi = min(T - 1, tq - w / 2 + w - 1);
+  const int lo = max(0, tq - w / 2), hi = min(L - 1, tq - w / 2 + w - 1);
   const size_t pair = ((size_t)k.b * T + tq) * H + k.h;
   f32x4 pv[2];   // the softmax weights of this lane's (query, key) pairs: requested with the rows, they do not depend on the product
 #pragma unroll
@@ -780,11 +831,11 @@ __global__ __launch_bounds__(256) void band_attn_bwd_q_mfma_kernel(const float* 
       const float ds = pv[tt][r] * (dp[tt][r] - dot) * scale;   // 0 outside the window (p == 0)
       dp[tt][r] = ds;
       const int slot = kb + 16 * tt + 4 * q + r - lo;
-      if (t < T && slot >= 0 && slot < w) dS[pair * w + slot] = ds;
+      if (t < L && slot >= 0 && slot < w) dS[pair * w + slot] = ds;
     }
   f32x4 out[HD / 16];
   band_rows_mma<HD>(dp, krows, out);   // dq = dS . K
-  band_store_rows<HD>(out, dqkv + (size_t)k.b * T * ld + k.h * HD, ld, k.i0, T, q, l15);
+  band_store_rows<HD>(out, dqkv + (size_t)k.b * T * ld + k.h * HD, ld, k.i0, L, T, q, l15);
 }
 
 // backward part 2 (MFMA): dk, dv for a block of 16 keys, gathered over the <= 16 + w - 1 queries that see them
@@ -793,16 +844,23 @@ __global__ __launch_bounds__(256) void band_attn_bwd_kv_mfma_kernel(const float*
                                                                     const float* __restrict__ dS,
                                                                     const float* __restrict__ dctx,
                                                                     float* __restrict__ dqkv, int B, int T, int D, int H,
-                                                                    int w) {
+                                                                    int w, const int32_t* __restrict__ lengths, int min_length) {
   const BandBlk k = band_block(B, T, H);
   if (!k.live) return;
   const int lane = threadIdx.x & 63, l15 = lane & 15, q = lane >> 4;
   const size_t ld = (size_t)3 * D;
+  float* dst = dqkv + (size_t)k.b * T * ld + k.h * HD;
+  const int L = row_length(lengths, min_length, k.b, T);
+  if (k.i0 >= L) {   // padding keys: no query sees them, dk = dv = 0
+    band_zero_rows<HD>(dst + D, ld, k.i0, T, q, l15);
+    band_zero_rows<HD>(dst + 2 * D, ld, k.i0, T, q, l15);
+    return;
+  }
   const int j = k.i0 + l15;                       // this lane's key (MFMA row of the coefficient operand)
   const int tb = k.i0 - (w - 1 - w / 2);          // first query of the tile pair: j-(w-1-w/2) <= t <= j+w/2
   BandRows<HD> qrows, grows;                      // the Q rows (dk) and the dctx rows (dv): requested before the coefficients
-  band_rows_load<HD>(qkv + (size_t)k.b * T * ld + k.h * HD, ld, tb, T, q, l15, qrows);
-  band_rows_load<HD>(dctx + (size_t)k.b * T * D + k.h * HD, (size_t)D, tb, T, q, l15, grows);
+  band_rows_load<HD>(qkv + (size_t)k.b * T * ld + k.h * HD, ld, tb, L, q, l15, qrows);
+  band_rows_load<HD>(dctx + (size_t)k.b * T * D + k.h * HD, (size_t)D, tb, L, q, l15, grows);
   f32x4 cds[2], cp[2];
 #pragma unroll
   for (int tt = 0; tt < 2; ++tt)
@@ -810,8 +868,8 @@ __global__ __launch_bounds__(256) void band_attn_bwd_kv_mfma_kernel(const float*
     for (int r = 0; r < 4; ++r) {
       const int t = tb + 16 * tt + 4 * q + r;
       float vds = 0.f, vp = 0.f;
-      if (t >= 0 && t < T && j < T) {
-        const int lo = max(0, t - w / 2), hi = min(T - 1, t - w / 2 + w - 1);
+      if (t >= 0 && t < L && j < L) {
+        const int lo = max(0, t - w / 2), hi = min(L - 1, t - w / 2 + w - 1);
         if (j >= lo && j <= hi) {
           const size_t pr = (((size_t)k.b * T + t) * H + k.h) * w + (j - lo);
           vds = dS[pr];
@@ -822,36 +880,36 @@ __global__ __launch_bounds__(256) void band_attn_bwd_kv_mfma_kernel(const float*
       cp[tt][r] = vp;
     }
   f32x4 out[HD / 16];
-  float* dst = dqkv + (size_t)k.b * T * ld + k.h * HD;
   band_rows_mma<HD>(cds, qrows, out);   // dk = dS^T . Q
-  band_store_rows<HD>(out, dst + D, ld, k.i0, T, q, l15);
+  band_store_rows<HD>(out, dst + D, ld, k.i0, L, T, q, l15);
   band_rows_mma<HD>(cp, grows, out);   // dv = P^T . dctx
-  band_store_rows<HD>(out, dst + 2 * D, ld, k.i0, T, q, l15);
+  band_store_rows<HD>(out, dst + 2 * D, ld, k.i0, L, T, q, l15);
 }
 
 // which == 0: forward, 1: backward-q, 2: backward-kv.  Returns false when the shape needs the generic kernels.
 template <int HD>
 void launch_band_mfma(int which, const float* qkv, float* ctx, float* P, const float* dctx, float* dqkv, float* dS, int B,
-                      int T, int D, int H, int w, hipStream_t st) {
+                      int T, int D, int H, int w, const int32_t* len, int minl, hipStream_t st) {
   const long waves = (long)B * ((T + 15) / 16) * H;
   const dim3 grid((unsigned)((waves + 3) / 4)), blk(256);
   if (which == 0)
-    hipLaunchKernelGGL((band_attn_fwd_mfma_kernel<HD>), grid, blk, 0, st, qkv, ctx, P, B, T, D, H, w);
+    hipLaunchKernelGGL((band_attn_fwd_mfma_kernel<HD>), grid, blk, 0, st, qkv, ctx, P, B, T, D, H, w, len, minl);
   else if (which == 1)
-    hipLaunchKernelGGL((band_attn_bwd_q_mfma_kernel<HD>), grid, blk, 0, st, qkv, (const float*)P, dctx, dqkv, dS, B, T, D, H, w);
+    hipLaunchKernelGGL((band_attn_bwd_q_mfma_kernel<HD>), grid, blk, 0, st, qkv, (const float*)P, dctx, dqkv, dS, B, T, D, H, w,
+                       len, minl);
   else
     hipLaunchKernelGGL((band_attn_bwd_kv_mfma_kernel<HD>), grid, blk, 0, st, qkv, (const float*)P, (const float*)dS, dctx, dqkv,
-                       B, T, D, H, w);
+                       B, T, D, H, w, len, minl);
 }
 bool band_mfma(int which, const float* qkv, float* ctx, float* P, const float* dctx, float* dqkv, float* dS, int B, int T,
-               int D, int H, int w, hipStream_t st) {
+               int D, int H, int w, const int32_t* len, int minl, hipStream_t st) {
   if (w > 17 || D % H) return false;
   switch (D / H) {
-    case 16: launch_band_mfma<16>(which, qkv, ctx, P, dctx, dqkv, dS, B, T, D, H, w, st); return true;
-    case 32: launch_band_mfma<32>(which, qkv, ctx, P, dctx, dqkv, dS, B, T, D, H, w, st); return true;
-    case 64: launch_band_mfma<64>(which, qkv, ctx, P, dctx, dqkv, dS, B, T, D, H, w, st); return true;
-    case 96: launch_band_mfma<96>(which, qkv, ctx, P, dctx, dqkv, dS, B, T, D, H, w, st); return true;
-    case 128: launch_band_mfma<128>(which, qkv, ctx, P, dctx, dqkv, dS, B, T, D, H, w, st); return true;
+    case 16: launch_band_mfma<16>(which, qkv, ctx, P, dctx, dqkv, dS, B, T, D, H, w, len, minl, st); return true;
+    case 32: launch_band_mfma<32>(which, qkv, ctx, P, dctx, dqkv, dS, B, T, D, H, w, len, minl, st); return true;
+    case 64: launch_band_mfma<64>(which, qkv, ctx, P, dctx, dqkv, dS, B, T, D, H, w, len, minl, st); return true;
+    case 96: launch_band_mfma<96>(which, qkv, ctx, P, dctx, dqkv, dS, B, T, D, H, w, len, minl, st); return true;
+    case 128: launch_band_mfma<128>(which, qkv, ctx, P, dctx, dqkv, dS, B, T, D, H, w, len, minl, st); return true;
     default: return false;
   }
 }
@@ -884,11 +942,16 @@ __device__ __forceinline__ void row_dots(const f32x4* __restrict__ hr, const f32
 }
 __global__ __launch_bounds__(256) void score_fwd_kernel(const float* __restrict__ h, const float* __restrict__ txt,
                                                         const float* __restrict__ clip, float* __restrict__ scores,
-                                                        int B, int T, int D, int M, float tau) {
+                                                        int B, int T, int D, int M, float tau,
+                                                        const int32_t* __restrict__ lengths, int min_length) {
   const int lane = threadIdx.x & 63;
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= (long)B * T) return;
   const int b = (int)(row / T);
+  if ((int)(row - (long)b * T) >= row_length(lengths, min_length, b, T)) {   // padding frame: never selected, probability 0
+    if (lane == 0) scores[row] = -INFINITY;
+    return;
+  }
   const f32x4* hr = reinterpret_cast<const f32x4*>(h + row * D);
   const int nv = D >> 2;   // D % 64 == 0
   float hh = 0.f, acc = 0.f, hn = 0.f;
@@ -924,7 +987,8 @@ __global__ __launch_bounds__(256) void score_bwd_kernel(const float* __restrict_
                                                         const float* __restrict__ dscores, float* __restrict__ dh,
                                                         int B, int T, int D, int M, float tau, int n_score,
                                                         const float* __restrict__ w1, float* __restrict__ w1t,
-                                                        const float* __restrict__ w2, float* __restrict__ w2t, PgIn pg) {
+                                                        const float* __restrict__ w2, float* __restrict__ w2t, PgIn pg,
+                                                        const int32_t* __restrict__ lengths, int min_length) {
   if ((int)blockIdx.x >= n_score) {
     __shared__ float tile[32][33];
     const int tpr = (D + 31) / 32;
@@ -950,6 +1014,12 @@ __global__ __launch_bounds__(256) void score_bwd_kernel(const float* __restrict_
   const f32x4* hr = reinterpret_cast<const f32x4*>(h + row * D);
   f32x4* dr = reinterpret_cast<f32x4*>(dh + row * D);
   const int nv = D >> 2;
+  if ((int)(row - (long)b * T) >= row_length(lengths, min_length, b, T)) {
+    // padding frame: dL/dscores = 0, so its dh2 row is exactly 0 - and with it the row's share of every weight and bias gradient
+    // the GEMMs behind this kernel form over all B*T rows (adv / loss are written by the wave of t = 0, never padding: L_b >= 1)
+    for (int c = lane; c < nv; c += 64) dr[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    return;
+  }
   // PG: what the policy-gradient term needs from memory is requested FIRST, with the row's own loads (round 5: the membership test
   // was a binary search in global memory behind everything else - five dependent round trips, the longest chain of the launch).
   // G * k <= 256 (the training shapes: 8 x 16): the wave reads the prompt's G sorted lists flat, lane l entries l, l + 64, ...
@@ -1785,9 +1855,10 @@ extern "C" size_t tspo_selector_workspace_bytes(int B, int T, int D, int H, int 
 static int selector_forward_impl(const tspo_selector_weights* w, const float* img, const float* txt,
                                  const float* clip, int B, int T, int D, int H, int M, int window, float tau,
                                  float* scores, float* temporal_attn, void* workspace, size_t workspace_bytes,
-                                 tspo_stream_t stream, int flags) {
+                                 tspo_stream_t stream, int flags, const int32_t* lengths = nullptr, int min_length = 0) {
   Prec prec;
   if (int e = sel_prec("selector_forward", 0, flags, D, &prec)) return e;
+  TSPO_REQUIRE(!lengths || (min_length >= 1 && min_length <= T), "selector_forward: min_length=%d must be in [1, T=%d]", min_length, T);
   TSPO_REQUIRE(w && img && txt && scores && workspace, "selector_forward: null pointer");
   TSPO_REQUIRE(w->wqkv && w->bqkv && w->w1 && w->b1 && w->w2 && w->b2, "selector_forward: null weight pointer");
   if (int e = check_dims("selector_forward", B, T, D, H, M, window)) return e;
@@ -1800,15 +1871,16 @@ static int selector_forward_impl(const tspo_selector_weights* w, const float* im
   const size_t tot = (size_t)BT * D;
   int nb = (int)((tot / 2 + 255) / 256);
   if (nb > 4096) nb = 4096;
-  hipLaunchKernelGGL(posenc_add_kernel, dim3(nb), dim3(256), 0, st, img, s.xpe, T, D, tot);
+  hipLaunchKernelGGL(posenc_add_kernel, dim3(nb), dim3(256), 0, st, img, s.xpe, T, D, tot, lengths, min_length);
   if (int e = launch_gemm_nt<EPI_NONE>(s.xpe, w->wqkv, w->bqkv, nullptr, s.qkv, BT, 3 * D, D, st, prec)) return e;
   const long pairs = (long)BT * H;
-  if (!band_mfma(0, s.qkv, s.ctx, s.P, nullptr, nullptr, nullptr, B, T, D, H, window, st))
+  if (!band_mfma(0, s.qkv, s.ctx, s.P, nullptr, nullptr, nullptr, B, T, D, H, window, lengths, min_length, st))
     hipLaunchKernelGGL(band_attn_fwd_kernel, dim3((unsigned)((pairs + 7) / 8)), dim3(256), 0, st, s.qkv, s.ctx, s.P, B, T,
-                       D, H, window);
+                       D, H, window, lengths, min_length);
   if (int e = launch_gemm_nt<EPI_RELU>(s.ctx, w->w1, w->b1, nullptr, s.h1, BT, D, D, st, prec)) return e;
   if (int e = launch_gemm_nt<EPI_RESID>(s.h1, w->w2, w->b2, img, s.h2, BT, D, D, st, prec)) return e;
-  hipLaunchKernelGGL(score_fwd_kernel, dim3((BT + 3) / 4), dim3(256), 0, st, s.h2, txt, clip, scores, B, T, D, M, tau);
+  hipLaunchKernelGGL(score_fwd_kernel, dim3((BT + 3) / 4), dim3(256), 0, st, s.h2, txt, clip, scores, B, T, D, M, tau,
+                     lengths, min_length);
   if (temporal_attn) {
     hipError_t e = hipMemcpyAsync(temporal_attn, s.h2, tot * sizeof(float), hipMemcpyDeviceToDevice, st);
     if (e != hipSuccess) return tspo::set_err(TSPO_ELAUNCH, "selector_forward: copy: %s", hipGetErrorString(e));
@@ -1829,6 +1901,13 @@ extern "C" int tspo_selector_forward_ex(const tspo_selector_weights* w, const fl
                                         tspo_stream_t stream, int flags) {
   return selector_forward_impl(w, img, txt, clip, B, T, D, H, M, window, tau, scores, temporal_attn, workspace,
                                workspace_bytes, stream, flags);
+}
+extern "C" int tspo_selector_forward_len(const tspo_selector_weights* w, const float* img, const float* txt,
+                                         const float* clip, int B, int T, int D, int H, int M, int window, float tau,
+                                         float* scores, float* temporal_attn, void* workspace, size_t workspace_bytes,
+                                         tspo_stream_t stream, int flags, const int32_t* lengths, int min_length) {
+  return selector_forward_impl(w, img, txt, clip, B, T, D, H, M, window, tau, scores, temporal_attn, workspace,
+                               workspace_bytes, stream, flags, lengths, min_length);
 }
 
 namespace {
@@ -1901,10 +1980,11 @@ static int selector_backward_impl(const tspo_selector_weights* w, const float* i
                                   const float* dscores, int B, int T, int D, int H, int M, int window, float tau,
                                   const tspo_selector_grads* g, void* workspace, size_t workspace_bytes,
                                   tspo_stream_t stream, int flags, const PgIn* pg = nullptr, float* norm_partials = nullptr,
-                                  int* n_partials = nullptr) {
+                                  int* n_partials = nullptr, const int32_t* lengths = nullptr, int min_length = 0) {
   const int accum = (flags & TSPO_SEL_ACCUMULATE) ? 1 : 0;
   Prec prec;
   if (int e = sel_prec("selector_backward", pg ? 2 : 1, flags, D, &prec)) return e;
+  TSPO_REQUIRE(!lengths || (min_length >= 1 && min_length <= T), "selector_backward: min_length=%d must be in [1, T=%d]", min_length, T);
   TSPO_REQUIRE(w && img && txt && (dscores || pg) && g && workspace, "selector_backward: null pointer");
   TSPO_REQUIRE(g->wqkv && g->bqkv && g->w1 && g->b1 && g->w2 && g->b2, "selector_backward: null grad pointer");
   if (int e = check_dims("selector_backward", B, T, D, H, M, window)) return e;
@@ -1921,10 +2001,10 @@ static int selector_backward_impl(const tspo_selector_weights* w, const float* i
   const int n_score = (BT + 3) / 4, tpr = (D + 31) / 32;
   if (pg)
     hipLaunchKernelGGL(score_bwd_kernel<true>, dim3(n_score + 2 * tpr * tpr), dim3(256), 0, st, s.h2, txt, nullptr, s.dh2, B, T,
-                       D, M, tau, n_score, w->w1, s.w1t, w->w2, s.w2t, *pg);
+                       D, M, tau, n_score, w->w1, s.w1t, w->w2, s.w2t, *pg, lengths, min_length);
   else
     hipLaunchKernelGGL(score_bwd_kernel<false>, dim3(n_score + 2 * tpr * tpr), dim3(256), 0, st, s.h2, txt, dscores, s.dh2, B,
-                       T, D, M, tau, n_score, w->w1, s.w1t, w->w2, s.w2t, PgIn{});
+                       T, D, M, tau, n_score, w->w1, s.w1t, w->w2, s.w2t, PgIn{}, lengths, min_length);
   // exact-fp32 (and bf16-operand) path with 128-divisible D: bias-gradient column sums come out of the weight-gradient kernels, and
   // each of the two DxD weight gradients shares a launch with the data-gradient GEMM that does not depend on it
   const bool fused = prec != PREC_BF16X3 && D % 128 == 0 && D % 96 == 0;
@@ -1962,12 +2042,12 @@ static int selector_backward_impl(const tspo_selector_weights* w, const float* i
   // banded attention
   const long pairs = (long)BT * H;
   const unsigned pb = (unsigned)((pairs + 7) / 8);
-  if (!band_mfma(1, s.qkv, nullptr, s.P, s.dctx, s.dqkv, s.dS, B, T, D, H, window, st))
+  if (!band_mfma(1, s.qkv, nullptr, s.P, s.dctx, s.dqkv, s.dS, B, T, D, H, window, lengths, min_length, st))
     hipLaunchKernelGGL(band_attn_bwd_q_kernel, dim3(pb), dim3(256), 0, st, s.qkv, s.P, s.dctx, s.dqkv, s.dS, B, T, D, H,
-                       window);
-  if (!band_mfma(2, s.qkv, nullptr, s.P, s.dctx, s.dqkv, s.dS, B, T, D, H, window, st))
+                       window, lengths, min_length);
+  if (!band_mfma(2, s.qkv, nullptr, s.P, s.dctx, s.dqkv, s.dS, B, T, D, H, window, lengths, min_length, st))
     hipLaunchKernelGGL(band_attn_bwd_kv_kernel, dim3(pb), dim3(256), 0, st, s.qkv, s.P, s.dS, s.dctx, s.dqkv, B, T, D, H,
-                       window);
+                       window, lengths, min_length);
   // q/k/v projections
   if (int e = weight_grad(s.dqkv, s.xpe, part_qkv, fused ? s.cpart + 2 * D : nullptr, cstride, BT, 3 * D, D, s, st, prec, fq))
     return e;
@@ -2041,6 +2121,20 @@ extern "C" int tspo_policy_backward_ex(const tspo_selector_weights* w, const flo
                                 flags, &pg, norm_partials, n_partials);
 }
 
+extern "C" int tspo_policy_backward_len(const tspo_selector_weights* w, const float* img, const float* txt, const float* rewards,
+                                        const float* logp, const int64_t* idx, int B, int T, int D, int H, int M, int window,
+                                        float tau, int G, int k, float adv_eps, float scale, const tspo_selector_grads* grads,
+                                        float* adv, float* loss, void* workspace, size_t workspace_bytes, tspo_stream_t stream,
+                                        int flags, float* norm_partials, int* n_partials, const int32_t* lengths,
+                                        int min_length) {
+  TSPO_REQUIRE(rewards && logp && idx && adv, "policy_backward: null pointer");
+  TSPO_REQUIRE(G >= 1 && G <= 64 && k >= 1 && k <= T, "policy_backward: bad dims G=%d (1..64) k=%d T=%d", G, k, T);
+  TSPO_REQUIRE(!norm_partials || n_partials, "policy_backward_len: norm_partials without n_partials");
+  const PgIn pg{rewards, logp, idx, G, k, adv_eps, scale, adv, loss};
+  return selector_backward_impl(w, img, txt, nullptr, B, T, D, H, M, window, tau, grads, workspace, workspace_bytes, stream,
+                                flags, &pg, norm_partials, n_partials, lengths, min_length);
+}
+
 extern "C" int tspo_selector_backward(const tspo_selector_weights* w, const float* img, const float* txt,
                                       const float* dscores, int B, int T, int D, int H, int M, int window, float tau,
                                       const tspo_selector_grads* g, void* workspace, size_t workspace_bytes,
@@ -2053,6 +2147,13 @@ extern "C" int tspo_selector_backward_ex(const tspo_selector_weights* w, const f
                                          tspo_stream_t stream, int flags) {
   return selector_backward_impl(w, img, txt, dscores, B, T, D, H, M, window, tau, g, workspace, workspace_bytes, stream,
                                 flags);
+}
+extern "C" int tspo_selector_backward_len(const tspo_selector_weights* w, const float* img, const float* txt,
+                                          const float* dscores, int B, int T, int D, int H, int M, int window, float tau,
+                                          const tspo_selector_grads* g, void* workspace, size_t workspace_bytes,
+                                          tspo_stream_t stream, int flags, const int32_t* lengths, int min_length) {
+  return selector_backward_impl(w, img, txt, dscores, B, T, D, H, M, window, tau, g, workspace, workspace_bytes, stream,
+                                flags, nullptr, nullptr, nullptr, lengths, min_length);
 }
 
 extern "C" int tspo_clip_scores(const float* txt, const float* feat, int B, int T, int D, int M, float* clip,

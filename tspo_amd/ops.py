@@ -51,6 +51,42 @@ def _check_rollout_idx(ix: torch.Tensor, what: str, need_group: bool = False) ->
         raise ValueError(f"{what}: idx[b,g,:] must be strictly ascending (sort each rollout's frame list first)")
 
 
+def _lengths_arg(lengths, min_length, B: int, T: int, device, what: str, k: Optional[int] = None):
+    """Per-video lengths of a padded batch (include/tspo_hip.h, the `_len` entries) -> (int32 [B] device tensor | None, min_length).
+    A host sequence is validated here (1 <= L_b <= T), uploaded once, and its minimum taken on the host.  An int32 device tensor
+    is passed through untouched - nothing is copied back - so the caller must vouch for `min_length` (the kernels clamp every
+    device value to [min_length, T]).  `k`: what a sampler selects per rollout; k > min_length is an error."""
+    if lengths is None:
+        if min_length is not None:
+            raise ValueError(f"{what}: min_length without lengths")
+        return None, 0
+    if isinstance(lengths, torch.Tensor) and lengths.is_cuda:
+        if min_length is None:
+            raise ValueError(f"{what}: device lengths need min_length (a host lower bound the caller vouches for; nothing is copied back)")
+        if lengths.dtype != torch.int32 or tuple(lengths.shape) != (B,) or not lengths.is_contiguous():
+            raise ValueError(f"{what}: device lengths must be a contiguous int32 [B={B}] tensor, got {lengths.dtype} {tuple(lengths.shape)}")
+        if lengths.device != torch.device(device):
+            raise ValueError(f"{what}: lengths are on {lengths.device}, the batch on {device}")
+        ml = int(min_length)
+    else:
+        host = [int(v) for v in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
+        if len(host) != B:
+            raise ValueError(f"{what}: {len(host)} lengths for B={B} videos")
+        if min(host) < 1 or max(host) > T:
+            raise ValueError(f"{what}: lengths must be in [1, T={T}], got {host}")
+        ml = min(host) if min_length is None else int(min_length)
+        if ml > min(host):
+            raise ValueError(f"{what}: min_length={ml} exceeds the shortest video ({min(host)})")
+        lengths = host
+    if not 1 <= ml <= T:
+        raise ValueError(f"{what}: min_length={ml} must be in [1, T={T}]")
+    if k is not None and k > ml:
+        raise RuntimeError(f"selected index k out of range (k={k} > min_length={ml})")  # torch.topk's error class
+    if not isinstance(lengths, torch.Tensor):
+        lengths = torch.tensor(lengths, dtype=torch.int32, device=device)
+    return lengths, ml
+
+
 # ---------------------------------------------------------------------------
 # samplers
 # ---------------------------------------------------------------------------
@@ -84,15 +120,18 @@ def binmax(scores: torch.Tensor, k: int) -> torch.Tensor:
 
 def gumbel_topk(logits: torch.Tensor, k: int, G: int = 1, noise: Optional[torch.Tensor] = None, seed: int = 0,
                 offset: int = 0, tau: float = 1.0, want_probs: bool = False, want_noise: bool = False,
-                prompts_per_offset: int = 0):
+                prompts_per_offset: int = 0, lengths=None, min_length: Optional[int] = None):
     """logits [B,T]; noise [B,G,T] or None (in-kernel Philox).  Returns dict with idx [B,G,k], logp [B,T]
     and optionally probs / noise [B,G,T].  prompts_per_offset = p > 0: the batch holds B / p micro-steps of p prompts;
-    group j draws what a separate call with offset + j would (coalesced micro-steps, bitwise the sequential rollouts)."""
+    group j draws what a separate call with offset + j would (coalesced micro-steps, bitwise the sequential rollouts).
+    lengths / min_length (`_lengths_arg`): row b is its first L_b entries - the rollouts, logp and probs of a call on
+    logits[b, :L_b] alone; logp padding is -inf, probs / noise padding 0."""
     _need_gpu(logits, noise)
     l = _f32c(logits)
     B, T = l.shape
     if k > T:
         raise RuntimeError(f"selected index k out of range (k={k} > T={T})")  # torch.topk's error class
+    ln, ml = _lengths_arg(lengths, min_length, B, T, l.device, "gumbel_topk", k=int(k))
     n = None
     if noise is not None:
         n = _f32c(noise)
@@ -105,6 +144,11 @@ def gumbel_topk(logits: torch.Tensor, k: int, G: int = 1, noise: Optional[torch.
     nout = torch.empty((B, G, T), dtype=torch.float32, device=dev) if want_noise else None
     if prompts_per_offset < 0 or (prompts_per_offset and B % prompts_per_offset):
         raise ValueError(f"prompts_per_offset={prompts_per_offset} does not divide B={B}")
+    if ln is not None:
+        check(_lib.lib().tspo_gumbel_topk_len(_ptr(l), _ptr(n), seed & (2 ** 64 - 1), offset & (2 ** 64 - 1), B, G, T, int(k),
+                                              float(tau), _ptr(idx), _ptr(logp), _ptr(probs), _ptr(nout), _stream(),
+                                              int(prompts_per_offset), _ptr(ln), ml), "tspo_gumbel_topk_len")
+        return {"idx": idx, "logp": logp, "probs": probs, "noise": nout}
     check(_lib.lib().tspo_gumbel_topk_ex(_ptr(l), _ptr(n), seed & (2 ** 64 - 1), offset & (2 ** 64 - 1), B, G, T, int(k),
                                          float(tau), _ptr(idx), _ptr(logp), _ptr(probs), _ptr(nout), _stream(),
                                          int(prompts_per_offset)),
@@ -137,9 +181,10 @@ def pg_grad_logits(logp: torch.Tensor, idx: torch.Tensor, adv: torch.Tensor, sca
     return dl, loss
 
 
-def grpo_pg_grad(rewards: torch.Tensor, logp: torch.Tensor, idx: torch.Tensor, scale: float = 1.0, eps: float = 1e-4):
+def grpo_pg_grad(rewards: torch.Tensor, logp: torch.Tensor, idx: torch.Tensor, scale: float = 1.0, eps: float = 1e-4,
+                 lengths=None, min_length: Optional[int] = None):
     """grpo_advantage + pg_grad_logits in one launch: rewards [B,G], logp [B,T], idx [B,G,k] ->
-    (adv [B,G], dlogits [B,T], loss [B]); identical results."""
+    (adv [B,G], dlogits [B,T], loss [B]); identical results.  lengths / min_length (`_lengths_arg`): dlogits[b, L_b:] = 0."""
     _need_gpu(rewards, logp, idx)
     r, lp = _f32c(rewards), _f32c(logp)
     ix = idx.to(torch.int64).contiguous()
@@ -151,6 +196,11 @@ def grpo_pg_grad(rewards: torch.Tensor, logp: torch.Tensor, idx: torch.Tensor, s
     adv = torch.empty_like(r)
     dl = torch.empty_like(lp)
     loss = torch.empty((B,), dtype=torch.float32, device=lp.device)
+    ln, ml = _lengths_arg(lengths, min_length, B, T, lp.device, "grpo_pg_grad")
+    if ln is not None:
+        check(_lib.lib().tspo_grpo_pg_grad_len(_ptr(r), _ptr(lp), _ptr(ix), B, G, T, k, float(eps), float(scale), _ptr(adv),
+                                               _ptr(dl), _ptr(loss), _stream(), _ptr(ln), ml), "tspo_grpo_pg_grad_len")
+        return adv, dl, loss
     check(_lib.lib().tspo_grpo_pg_grad(_ptr(r), _ptr(lp), _ptr(ix), B, G, T, k, float(eps), float(scale), _ptr(adv), _ptr(dl),
                                        _ptr(loss), _stream()), "tspo_grpo_pg_grad")
     return adv, dl, loss
@@ -225,9 +275,12 @@ def _sel_flags(precision: str, accumulate: bool = False, forward: bool = False) 
 
 def selector_forward(flat: torch.Tensor, img: torch.Tensor, txt: torch.Tensor, clip: Optional[torch.Tensor],
                      H: int, window: int, tau: float, want_attn: bool = True, ws: Optional[torch.Tensor] = None,
-                     precision: str = "fp32"):
+                     precision: str = "fp32", lengths=None, min_length: Optional[int] = None):
     """flat: f32 parameter bucket (FLAT_LAYOUT). img [B,T,D], txt [B,M,D], clip [B,T] ->
     (scores [B,T] f32, temporal_attn [B,T,D] f32 | None, workspace).
+    lengths / min_length (`_lengths_arg`): videos of different lengths right-padded to T - video b is scored as if it were alone
+    with T = L_b, scores[b, L_b:] = -inf; padding rows of img / clip must be finite and influence nothing; the backward of this
+    workspace must get the same lengths (the padding contract: include/tspo_hip.h).
     precision="bf16x3" (opt-in, training): split-precision GEMMs on the bf16 MFMA, ~1e-5 relative error.
     precision="bf16" (opt-in, inference): the reference's own inference precision (gen_id_tspo.py:55) - GEMM operands rounded to
     bf16, fp32 accumulation, fp32 between the GEMMs; a workspace written by it is NOT valid for a backward.
@@ -244,6 +297,12 @@ def selector_forward(flat: torch.Tensor, img: torch.Tensor, txt: torch.Tensor, c
     scores = torch.empty((B, T), dtype=torch.float32, device=x.device)
     attn = torch.empty((B, T, D), dtype=torch.float32, device=x.device) if want_attn else None
     w = _sel_structs(flat, D, _lib.SelectorWeights)
+    ln, ml = _lengths_arg(lengths, min_length, B, T, x.device, "selector_forward")
+    if ln is not None:
+        check(_lib.lib().tspo_selector_forward_len(C.byref(w), _ptr(x), _ptr(e), _ptr(c), B, T, D, H, M, int(window), float(tau),
+                                                   _ptr(scores), _ptr(attn), _ptr(ws), ws.numel(), _stream(),
+                                                   _sel_flags(precision, forward=True), _ptr(ln), ml), "tspo_selector_forward_len")
+        return scores, attn, ws
     check(_lib.lib().tspo_selector_forward_ex(C.byref(w), _ptr(x), _ptr(e), _ptr(c), B, T, D, H, M, int(window), float(tau),
                                               _ptr(scores), _ptr(attn), _ptr(ws), ws.numel(), _stream(),
                                               _sel_flags(precision, forward=True)), "tspo_selector_forward")
@@ -251,15 +310,22 @@ def selector_forward(flat: torch.Tensor, img: torch.Tensor, txt: torch.Tensor, c
 
 
 def selector_backward(flat: torch.Tensor, flat_grad: torch.Tensor, img, txt, dscores, H, window, tau, ws,
-                      precision: str = "fp32", accumulate: bool = False):
+                      precision: str = "fp32", accumulate: bool = False, lengths=None, min_length: Optional[int] = None):
     """Writes the gradient of every trainable tensor into `flat_grad` (same layout as `flat`); accumulate=True ADDS it to what
-    `flat_grad` holds (gradient accumulation without a scratch bucket).  `precision` must be the one of the forward that wrote `ws`."""
+    `flat_grad` holds (gradient accumulation without a scratch bucket).  `precision` and `lengths` / `min_length` must be the ones
+    of the forward that wrote `ws`."""
     _need_gpu(flat, flat_grad, img, txt, dscores, ws)
     x, e, d = _f32c(img), _f32c(txt), _f32c(dscores)
     B, T, D = x.shape
     M = e.shape[1]
     w = _sel_structs(flat, D, _lib.SelectorWeights)
     g = _sel_structs(flat_grad, D, _lib.SelectorGrads)
+    ln, ml = _lengths_arg(lengths, min_length, B, T, x.device, "selector_backward")
+    if ln is not None:
+        check(_lib.lib().tspo_selector_backward_len(C.byref(w), _ptr(x), _ptr(e), _ptr(d), B, T, D, H, M, int(window), float(tau),
+                                                    C.byref(g), _ptr(ws), ws.numel(), _stream(), _sel_flags(precision, accumulate),
+                                                    _ptr(ln), ml), "tspo_selector_backward_len")
+        return
     check(_lib.lib().tspo_selector_backward_ex(C.byref(w), _ptr(x), _ptr(e), _ptr(d), B, T, D, H, M, int(window), float(tau),
                                                C.byref(g), _ptr(ws), ws.numel(), _stream(), _sel_flags(precision, accumulate)),
           "tspo_selector_backward")
@@ -267,12 +333,13 @@ def selector_backward(flat: torch.Tensor, flat_grad: torch.Tensor, img, txt, dsc
 
 def policy_backward(flat: torch.Tensor, flat_grad: torch.Tensor, img, txt, rewards, logp, idx, H, window, tau, ws,
                     scale: float = 1.0, eps: float = 1e-4, precision: str = "fp32", norm_partials: Optional[torch.Tensor] = None,
-                    accumulate: bool = False):
+                    accumulate: bool = False, lengths=None, min_length: Optional[int] = None):
     """grpo_pg_grad + selector_backward with one launch less (the score-gradient kernel derives dL/dscores from the
     rollouts itself): -> (adv [B,G], loss [B]); gradients go to `flat_grad` (equal to the two-call form to rounding).
     norm_partials (f32 [>=2048]): the backward's last kernel also leaves the gradient's partial sums of squares there
     and the call returns (adv, loss, n_partials) - feed them to adamw_clip_step(norm_partials=...) (one launch).
-    accumulate=True ADDS the gradients to `flat_grad` (second.. micro-step of an accumulation window)."""
+    accumulate=True ADDS the gradients to `flat_grad` (second.. micro-step of an accumulation window).
+    lengths / min_length (`_lengths_arg`): the ones of the forward that wrote `ws` (padded batch of videos of different lengths)."""
     _need_gpu(flat, flat_grad, img, txt, rewards, logp, idx, ws)
     x, e, r, lp = _f32c(img), _f32c(txt), _f32c(rewards), _f32c(logp)
     ix = idx.to(torch.int64).contiguous()
@@ -286,10 +353,20 @@ def policy_backward(flat: torch.Tensor, flat_grad: torch.Tensor, img, txt, rewar
     g = _sel_structs(flat_grad, D, _lib.SelectorGrads)
     adv = torch.empty_like(r)
     loss = torch.empty((B,), dtype=torch.float32, device=x.device)
+    ln, ml = _lengths_arg(lengths, min_length, B, T, x.device, "policy_backward")
     if norm_partials is not None:
         _need_gpu(norm_partials)
         if norm_partials.dtype != torch.float32 or norm_partials.numel() < 2048:
             raise ValueError("norm_partials must be a float32 tensor of >= 2048 elements")
+    if ln is not None:
+        npart = C.c_int(0)
+        check(_lib.lib().tspo_policy_backward_len(C.byref(w), _ptr(x), _ptr(e), _ptr(r), _ptr(lp), _ptr(ix), B, T, D, H, M,
+                                                  int(window), float(tau), G, k, float(eps), float(scale), C.byref(g), _ptr(adv),
+                                                  _ptr(loss), _ptr(ws), ws.numel(), _stream(), _sel_flags(precision, accumulate),
+                                                  _ptr(norm_partials), C.byref(npart) if norm_partials is not None else None,
+                                                  _ptr(ln), ml), "tspo_policy_backward_len")
+        return (adv, loss, int(npart.value)) if norm_partials is not None else (adv, loss)
+    if norm_partials is not None:
         npart = C.c_int(0)
         check(_lib.lib().tspo_policy_backward_ex(C.byref(w), _ptr(x), _ptr(e), _ptr(r), _ptr(lp), _ptr(ix), B, T, D, H, M,
                                                  int(window), float(tau), G, k, float(eps), float(scale), C.byref(g), _ptr(adv),

@@ -79,9 +79,10 @@ class RolloutContext:
     of THAT forward, the shapes / temperature they belong to, and the parameter version they were computed with.
     Opaque to callers; `PolicyTrainer.backward` validates and consumes it (a context is good for one backward)."""
     __slots__ = ("ws", "shape", "M", "tau", "param_version", "serial", "consumed", "owner", "idx", "idx_version", "micro_steps",
-                 "precision")
+                 "precision", "lengths", "min_length")
 
-    def __init__(self, ws, shape, M, tau, param_version, serial, owner, idx=None, micro_steps=1, precision="fp32"):
+    def __init__(self, ws, shape, M, tau, param_version, serial, owner, idx=None, micro_steps=1, precision="fp32",
+                 lengths=None, min_length=None):
         self.ws, self.shape, self.M, self.tau = ws, tuple(shape), M, float(tau)
         self.param_version, self.serial, self.consumed, self.owner = param_version, serial, False, owner
         # the index tensor this rollout emitted (ascending by construction) - the TENSOR, which also pins its storage, and its
@@ -89,6 +90,8 @@ class RolloutContext:
         self.idx, self.idx_version = idx, (idx._version if idx is not None else -1)
         self.micro_steps = int(micro_steps)  # how many micro-steps of the accumulation window this batch holds
         self.precision = precision           # GEMM precision of the forward that wrote `ws` (its backward must use the same)
+        # padded batch of videos of different lengths: the int32 device tensor and the host lower bound the forward ran with
+        self.lengths, self.min_length = lengths, min_length
 
 
 class PolicyTrainer:
@@ -109,6 +112,10 @@ class PolicyTrainer:
     micro-steps - one forward, one sampler launch, one backward instead of n.  The reference's configuration
     (per_device_train_batch_size 1 x gradient_accumulation_steps 2, train_deepspeed.sh:30-31): 15 launches per optimizer step
     instead of 28.  `tspo_amd.train` does this whenever the micro-batches of a window stack.
+
+    Videos of different lengths.  `rollout(..., lengths=[L_0, ..])` takes a batch right-padded to the longest video (ops:
+    `_lengths_arg`, include/tspo_hip.h: the `_len` entries): every prompt is scored, sampled and differentiated as if it were alone
+    with T = L_b, so the micro-steps of a window need not share T to run as one batch (`micro_steps=n` as above).
     """
 
     def __init__(self, flat: torch.Tensor, dim: int = 768, heads: int = 8, window_size: int = 12,
@@ -171,11 +178,15 @@ class PolicyTrainer:
         return (self.seed + 0x9E3779B97F4A7C15 * self.rank()) & (2 ** 64 - 1)
 
     # ---- micro-step ---------------------------------------------------------------------------------------
-    def rollout(self, feats, txt, clip, G: int, k: int, tau: float, noise=None, micro_steps: int = 1):
+    def rollout(self, feats, txt, clip, G: int, k: int, tau: float, noise=None, micro_steps: int = 1, lengths=None,
+                min_length: Optional[int] = None):
         """scores once, G Gumbel-top-k rollouts per prompt in one launch (tspo_trainer.py:508-537).
         Returns (scores [B,T], idx [B,G,k], logp [B,T], ctx) - pass `ctx` to the matching backward().
-        micro_steps = n > 1: the batch stacks the prompts of n micro-steps of this accumulation window (class docstring)."""
+        micro_steps = n > 1: the batch stacks the prompts of n micro-steps of this accumulation window (class docstring).
+        lengths (host sequence, or an int32 device tensor together with min_length): the frames of each video of a padded batch;
+        the context keeps them for the backward."""
         B, T, D = feats.shape
+        lengths, min_length = ops._lengths_arg(lengths, min_length, B, T, feats.device, "rollout", k=int(k))
         n = int(micro_steps)
         if n < 1 or B % n or (n > 1 and self._micro + n > self.grad_accum_steps):
             raise ValueError(f"rollout(micro_steps={n}): B={B} must be a multiple of it and {self._micro} + {n} micro-steps must fit "
@@ -189,13 +200,17 @@ class PolicyTrainer:
         if ws is None:
             ws = torch.empty((need,), dtype=torch.uint8, device=feats.device)
         scores, _, _ = ops.selector_forward(self.flat, feats, txt, clip, self.heads, self.window, tau, want_attn=False,
-                                            ws=ws, precision=self.gemm_precision)
+                                            ws=ws, precision=self.gemm_precision, **self._len_kw(lengths, min_length))
         out = ops.gumbel_topk(scores, k, G, noise=noise, seed=self._rank_seed(), offset=self._rollouts,
-                              prompts_per_offset=B // n if n > 1 else 0)
+                              prompts_per_offset=B // n if n > 1 else 0, **self._len_kw(lengths, min_length))
         ctx = RolloutContext(ws, (B, T, D), txt.shape[1], tau, self._param_version, self._rollouts, self, out["idx"], n,
-                             precision=self.gemm_precision)
+                             precision=self.gemm_precision, lengths=lengths, min_length=min_length if lengths is not None else None)
         self._rollouts += n
         return scores, out["idx"], out["logp"], ctx
+
+    @staticmethod
+    def _len_kw(lengths, min_length) -> Dict[str, object]:
+        return {} if lengths is None else {"lengths": lengths, "min_length": min_length}
 
     def backward(self, ctx: RolloutContext, feats, txt, logp, idx, rewards) -> Dict[str, torch.Tensor]:
         """advantage -> closed-form dL/dlogits -> selector backward, accumulated into the flat gradient bucket
@@ -227,6 +242,7 @@ class PolicyTrainer:
         target, acc = self.grad, self._micro > 0
         scale = 1.0 / ((B // n) * self.grad_accum_steps)      # every micro-step weighs 1 / accum, its prompts 1 / B_micro
         self._norm_np = 0
+        lkw = self._len_kw(ctx.lengths, ctx.min_length)
         # single rank, the whole accumulation window in this one backward, default exchange: nothing touches the bucket between
         # this backward and AdamW, so the backward's last kernel (the split reduction that writes the bucket) also leaves its
         # sum of squares
@@ -235,19 +251,19 @@ class PolicyTrainer:
         if idx.shape[1] <= 64 and fuse_norm:
             adv, loss, self._norm_np = ops.policy_backward(self.flat, target, feats, txt, rewards, logp, idx, self.heads,
                                                            self.window, ctx.tau, ctx.ws, scale=scale,
-                                                           precision=self.gemm_precision, norm_partials=self._norm_part)
+                                                           precision=self.gemm_precision, norm_partials=self._norm_part, **lkw)
             self._norm_grad_version = self.grad._version
         elif idx.shape[1] <= 64:    # advantage -> dL/dscores inside the backward's first kernel (one launch less)
             adv, loss = ops.policy_backward(self.flat, target, feats, txt, rewards, logp, idx, self.heads, self.window, ctx.tau,
-                                            ctx.ws, scale=scale, precision=self.gemm_precision, accumulate=acc)
+                                            ctx.ws, scale=scale, precision=self.gemm_precision, accumulate=acc, **lkw)
         else:
-            adv, dlog, loss = ops.grpo_pg_grad(rewards, logp, idx, scale=scale)
+            adv, dlog, loss = ops.grpo_pg_grad(rewards, logp, idx, scale=scale, **lkw)
             ops.selector_backward(self.flat, target, feats, txt, dlog, self.heads, self.window, ctx.tau, ctx.ws,
-                                  precision=self.gemm_precision, accumulate=acc)
+                                  precision=self.gemm_precision, accumulate=acc, **lkw)
         self._micro += n
         ctx.consumed = True
         self._ws_pool.append(ctx.ws)
-        ctx.ws, ctx.idx = None, None
+        ctx.ws, ctx.idx, ctx.lengths = None, None, None
         # `loss` is the kernels' UNSCALED per-prompt -sum(adv*...)/G (only dL/dscores carries `scale`): callers average it
         # over micro-steps themselves (train.py), so it is returned as is whatever grad_accum_steps is
         return {"loss": loss, "advantages": adv}
@@ -289,8 +305,9 @@ class PolicyTrainer:
         return stats
 
     def step(self, feats, txt, clip, reward_fn: Callable[[torch.Tensor], torch.Tensor], G: int, k: int, tau: float,
-             noise=None, lr: Optional[float] = None, micro_steps: int = 1):
-        scores, idx, logp, ctx = self.rollout(feats, txt, clip, G, k, tau, noise, micro_steps=micro_steps)
+             noise=None, lr: Optional[float] = None, micro_steps: int = 1, lengths=None, min_length: Optional[int] = None):
+        scores, idx, logp, ctx = self.rollout(feats, txt, clip, G, k, tau, noise, micro_steps=micro_steps, lengths=lengths,
+                                              min_length=min_length)
         rewards = reward_fn(idx)                      # [B,G] - the frozen video-LLM pass lives here (stock PyTorch)
         stats = self.update(ctx, feats, txt, logp, idx, rewards, lr)
         stats.update(scores=scores, idx=idx, rewards=rewards)

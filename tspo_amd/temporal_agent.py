@@ -53,10 +53,12 @@ class _SelectorFn(torch.autograd.Function):
     """autograd bridge: forward/backward are the HIP selector kernels."""
 
     @staticmethod
-    def forward(ctx, module, img, txt, clip, window, tau, *params):
+    def forward(ctx, module, img, txt, clip, window, tau, lengths, min_length, *params):
         flat = module._flat_params(training=True)   # (grad mode is off inside Function.forward; this IS the training path)
         prec = module.training_gemm_precision
-        scores, attn, ws = ops.selector_forward(flat, img, txt, clip, module.num_heads, window, tau, precision=prec)
+        # (lengths: already the int32 device tensor + host minimum of ops._lengths_arg, or None - the backward reuses them)
+        ctx.len_kw = {} if lengths is None else {"lengths": lengths, "min_length": min_length}
+        scores, attn, ws = ops.selector_forward(flat, img, txt, clip, module.num_heads, window, tau, precision=prec, **ctx.len_kw)
         ctx.module, ctx.window, ctx.tau, ctx.ws, ctx.precision = module, window, tau, ws, prec
         ctx.save_for_backward(img, txt)
         # the backward needs the weights THIS forward used.  Packed copy of non-flat parameters: it is repacked in place on
@@ -79,13 +81,13 @@ class _SelectorFn(torch.autograd.Function):
                                "its backward (optimizer step / EMA swap with a graph still alive); run the forward again")
         fg = torch.zeros_like(ctx.flat)
         ops.selector_backward(ctx.flat, fg, img, txt, dscores.contiguous(), m.num_heads, ctx.window, ctx.tau, ctx.ws,
-                              precision=ctx.precision)
+                              precision=ctx.precision, **ctx.len_kw)
         offs = ops.flat_offsets(m.dim)
         grads = []
         for name, p in m._trainable_named():
             off, shape = offs[name]
             grads.append(fg[off:off + p.numel()].view(shape).to(p.dtype))
-        return (None, None, None, None, None, None, *grads)
+        return (None, None, None, None, None, None, None, None, *grads)
 
 
 class MultiModal_Align(nn.Module):
@@ -237,14 +239,20 @@ class MultiModal_Align(nn.Module):
                                             score_tau)
         return scores[0].to(input_emb.dtype), attn.to(input_emb.dtype)
 
-    def forward_batched(self, img, txt, clip, window_size, score_tau=0.025):
-        """img [B,T,D], txt [B,M,D], clip [B,T] -> (scores f32 [B,T], temporal_attn f32 [B,T,D])."""
+    def forward_batched(self, img, txt, clip, window_size, score_tau=0.025, lengths=None, min_length=None):
+        """img [B,T,D], txt [B,M,D], clip [B,T] -> (scores f32 [B,T], temporal_attn f32 [B,T,D]).
+        lengths (host sequence, or an int32 device tensor together with min_length; ops._lengths_arg): videos of different lengths
+        right-padded to T - video b is scored as if it were alone with T = L_b; scores[b, L_b:] = -inf, temporal_attn[b, L_b:] is
+        unspecified, and padding frames receive and cause no gradient."""
+        B, T = img.shape[:2]
+        lengths, min_length = ops._lengths_arg(lengths, min_length, B, T, img.device, "forward_batched")
         params = [p for _, p in self._trainable_named()]
         if torch.is_grad_enabled() and any(p.requires_grad for p in params):
             self._realias_grads()
-            return _SelectorFn.apply(self, img, txt, clip, int(window_size), float(score_tau), *params)
+            return _SelectorFn.apply(self, img, txt, clip, int(window_size), float(score_tau), lengths, min_length, *params)
+        kw = {} if lengths is None else {"lengths": lengths, "min_length": min_length}
         scores, attn, _ = ops.selector_forward(self._flat_params(), img, txt, clip, self.num_heads, int(window_size),
-                                               float(score_tau), precision=self.inference_gemm_precision)
+                                               float(score_tau), precision=self.inference_gemm_precision, **kw)
         return scores, attn
 
 

@@ -62,6 +62,7 @@ class TrainConfig:
     heads: int = 8
     gemm_precision: str = "fp32"
     coalesce_micro_steps: bool = True      # run the micro-steps of an optimizer step as one stacked batch when their shapes allow
+    pad_variable_length: bool = False      # ... and, when only their video lengths differ, as one batch padded to the longest video
 
 
 class Batch:
@@ -70,10 +71,17 @@ class Batch:
     nothing to say).  The same convention holds for a single micro-batch and for the stacked batch of a coalesced accumulation
     window (round 6, ADVICE r5: a reward plug-in that reads `batch.meta[b]` sees the same thing on stacked and unstacked steps).
     `frames` (optional, FrameDataset sets it): a list of length B whose entry b is `(pool, plan)` - the prompt's uint8 frame pool
-    on the device and the int64 index plan [T] with `pool[plan[t]]` = frame t of the video the policy scored - or None."""
+    on the device and the int64 index plan [T] with `pool[plan[t]]` = frame t of the video the policy scored - or None.
+    `lengths` (optional): a list of B ints - the batch holds videos of different lengths right-padded to T (zeros in feats / clip,
+    False in mask); prompt b has lengths[b] frames and the policy step treats it as if it were alone (`_pad_stack`)."""
 
-    def __init__(self, feats, txt, clip, mask, item_type="specific", meta=None, frames=None):
+    def __init__(self, feats, txt, clip, mask, item_type="specific", meta=None, frames=None, lengths=None):
         B = feats.shape[0]
+        if lengths is not None:
+            lengths = [int(v) for v in lengths]
+            if len(lengths) != B or min(lengths) < 1 or max(lengths) > feats.shape[1]:
+                raise ValueError(f"Batch.lengths must hold one length in [1, T={feats.shape[1]}] per prompt (B={B}), got {lengths}")
+        self.lengths = lengths
         if frames is not None and (not isinstance(frames, list) or len(frames) != B):
             raise ValueError(f"Batch.frames must be a list with one (pool, plan) entry per prompt (B={B})")
         self.frames = frames
@@ -189,11 +197,13 @@ class FrameDataset:
     `distractors(n_clips, clip_len, like, seed)` are injectable (the reference's sample_real_frames needs a video corpus).
     Random streams are seeded per (seed, global item index): a resumed run draws the haystacks a straight run draws.
     `record=True` keeps (global item index, plan, mask) of every item prepared in `history` (off by default: it grows with
-    the run)."""
+    the run).  `pad_batches=True` lets `batches(bs > 1)` yield padded micro-batches (`Batch.lengths`); without it bs > 1 raises."""
+
+    pad_batches = False
 
     def __init__(self, items: Sequence[dict], model, clip_processor, video_root: str = "", load_video=None, distractors=None,
                  seed: int = 0, device="cuda", sample_len: int = 50, n_distractor_clips: int = 12, max_frames_num: int = 128,
-                 record: bool = False):
+                 record: bool = False, pad_batches: bool = False):
         from . import haystack
         from .preprocess import PreprocessSpec
         if not items:
@@ -209,6 +219,7 @@ class FrameDataset:
         self.seed, self.dev, self.spec = int(seed), torch.device(device), spec
         self.sample_len, self.n_clips, self.max_frames = sample_len, n_distractor_clips, max_frames_num
         self.record, self.history = bool(record), []
+        self.pad_batches = bool(pad_batches)   # batches(bs > 1): micro-batches of bs haystacks padded to the longest (opt-in)
 
     def item_seed(self, gi: int) -> int:
         return (self.seed * 1_000_003 + gi) % (2 ** 32)
@@ -241,13 +252,18 @@ class FrameDataset:
                      [{"video": it["video"], "item": gi, "n_video_frames": L}], frames=[(pool, plan_d)])
 
     def batches(self, rank: int, world: int, bs: int, skip: int = 0) -> Iterator[Batch]:
-        """`skip` = micro-batches already consumed (resume): the item cursor advances, nothing is read or decoded for them."""
-        if bs != 1:
+        """`skip` = micro-batches already consumed (resume): the item cursor advances, nothing is read or decoded for them.
+        bs > 1 (pad_batches=True only): micro-batch i holds items i * bs .. i * bs + bs - 1 of this rank's stream, padded to the
+        longest haystack (`_pad_stack`); they must be of one item type (k depends on it), as `_pad_stack` says when they are not."""
+        if bs != 1 and not self.pad_batches:
             raise ValueError("FrameDataset: haystacks differ in length (T = 50 x (r + 12)): one prompt per micro-batch, like the "
                              f"reference (per_device_train_batch_size 1), got {bs}")
         i = int(skip)
         while True:
-            yield self.prepare(i * world + rank)
+            if bs == 1:
+                yield self.prepare(i * world + rank)
+            else:
+                yield _pad_stack([self.prepare((i * bs + j) * world + rank) for j in range(bs)])
             i += 1
 
 
@@ -265,7 +281,8 @@ class PretokenizedProcessor:
         return BatchEncoding({"input_ids": ids, "attention_mask": torch.ones_like(ids)})
 
 
-def frame_dataset_from_dir(frame_dir: str, model_dir: Optional[str], seed: int, device, record: bool = False) -> FrameDataset:
+def frame_dataset_from_dir(frame_dir: str, model_dir: Optional[str], seed: int, device, record: bool = False,
+                           pad_batches: bool = False) -> FrameDataset:
     """`--frame-dir <dir>`: `<dir>/items.json` (a list of annotation items; `video` relative to <dir>) + uint8 [L,H,W,3] `.npy`
     videos.  The TSPOModel (CLIP towers; its selector is the policy that trains) is loaded from `model_dir` (default
     `<dir>/model`), and so is the CLIP processor - unless every item carries `input_ids`, then no tokenizer is needed."""
@@ -281,13 +298,21 @@ def frame_dataset_from_dir(frame_dir: str, model_dir: Optional[str], seed: int, 
     else:
         from transformers import CLIPProcessor
         proc = CLIPProcessor.from_pretrained(model_dir)
-    return FrameDataset(items, model, proc, video_root=frame_dir, seed=seed, device=device, record=record)
+    return FrameDataset(items, model, proc, video_root=frame_dir, seed=seed, device=device, record=record, pad_batches=pad_batches)
 
 
 def _stackable(window: List[Batch]) -> bool:
     a = window[0]
-    return len(window) > 1 and all(b.feats.shape == a.feats.shape and b.txt.shape == a.txt.shape and b.mask.shape == a.mask.shape
-                                   and b.item_type == a.item_type for b in window[1:])
+    return len(window) > 1 and all(b.lengths is None for b in window) and all(
+        b.feats.shape == a.feats.shape and b.txt.shape == a.txt.shape and b.mask.shape == a.mask.shape
+        and b.item_type == a.item_type for b in window[1:])
+
+
+def _paddable(window: List[Batch]) -> bool:
+    """The batches differ at most in their video lengths: same prompts per batch, feature width, text rows and item type (hence k)."""
+    a = window[0]
+    return len(window) > 1 and all(b.feats.shape[0] == a.feats.shape[0] and b.feats.shape[2] == a.feats.shape[2]
+                                   and b.txt.shape == a.txt.shape and b.item_type == a.item_type for b in window[1:])
 
 
 def _stack(window: List[Batch]) -> Batch:
@@ -295,6 +320,28 @@ def _stack(window: List[Batch]) -> Batch:
                  torch.cat([b.mask for b in window]), window[0].item_type, [m for b in window for m in b.meta],
                  None if all(b.frames is None for b in window) else
                  [f for b in window for f in (b.frames if b.frames is not None else [None] * b.feats.shape[0])])
+
+
+def _pad_stack(window: List[Batch]) -> Batch:
+    """`_stack` for batches whose videos differ in length (`_paddable`): feats / clip right-padded with zeros and mask with False to
+    the longest video, `lengths` = the frames of every prompt (a batch that is padded already keeps its own); meta and frames in
+    window order, like `_stack`."""
+    if not _paddable(window):
+        raise ValueError("_pad_stack: the batches must agree in prompts per batch, feature width, text rows and item type")
+    T = max(b.feats.shape[1] for b in window)
+
+    def pad(x, fill):
+        if x.shape[1] == T:
+            return x
+        out = x.new_full((x.shape[0], T) + tuple(x.shape[2:]), fill)
+        out[:, :x.shape[1]] = x
+        return out
+    lengths = [L for b in window for L in (b.lengths if b.lengths is not None else [b.feats.shape[1]] * b.feats.shape[0])]
+    return Batch(torch.cat([pad(b.feats, 0.0) for b in window]), torch.cat([b.txt for b in window]),
+                 torch.cat([pad(b.clip, 0.0) for b in window]), torch.cat([pad(b.mask, False) for b in window]),
+                 window[0].item_type, [m for b in window for m in b.meta],
+                 None if all(b.frames is None for b in window) else
+                 [f for b in window for f in (b.frames if b.frames is not None else [None] * b.feats.shape[0])], lengths=lengths)
 
 
 def mask_reward_model(idx: torch.Tensor, batch: Batch) -> torch.Tensor:
@@ -373,12 +420,21 @@ def train(cfg: TrainConfig, data, reward_model: Callable[[torch.Tensor, Batch], 
         # their batches stack - same T, text rows, item type (hence k) - they run as ONE rollout / backward of the stacked batch
         # (PolicyTrainer, "coalesced micro-steps": same Philox draws per prompt as the sequential path, 15 launches instead of 28
         # for the reference's 1 x 2 configuration).  Videos of different length (feature caches) keep one micro-step each.
-        groups = [window] if cfg.coalesce_micro_steps and _stackable(window) else [[b] for b in window]
+        # With pad_variable_length such a window runs as one batch all the same, padded to its longest video (`_pad_stack`): every
+        # prompt is computed as if it were alone, with the rollouts of the sequential path.
+        padded = False
+        if cfg.coalesce_micro_steps and _stackable(window):
+            groups = [window]
+        elif cfg.pad_variable_length and _paddable(window):
+            groups, padded = [window], True
+        else:
+            groups = [[b] for b in window]
         acc = torch.zeros(len(tdist.METRIC_KEYS) + len(REWARD_NAMES), dtype=torch.float32, device=dev)   # metrics stay on the device
         for grp in groups:
-            b = grp[0] if len(grp) == 1 else _stack(grp)
+            b = grp[0] if len(grp) == 1 else (_pad_stack(grp) if padded else _stack(grp))
             k = rewards.training_sample_len(cfg.training_sample_len, b.item_type)
-            scores, idx, logp, ctx = trainer.rollout(b.feats, b.txt, b.clip, cfg.num_generations, k, tau, micro_steps=len(grp))
+            scores, idx, logp, ctx = trainer.rollout(b.feats, b.txt, b.clip, cfg.num_generations, k, tau, micro_steps=len(grp),
+                                                     lengths=b.lengths)
             rpf = reward_model(idx, b)                                           # [B, G, F]   (frozen video-LLM plug-in)
             B, G, F = rpf.shape
             rew = rewards.combine_rewards(rpf.reshape(B * G, F), b.item_type).reshape(B, G)
@@ -447,7 +503,7 @@ def main(argv=None):
             ap.error("--frame-dir and --features exclude each other")
         local = int(os.environ.get("LOCAL_RANK", "0"))
         dev = torch.device("cuda", local if torch.cuda.device_count() > local else 0)
-        data = frame_dataset_from_dir(a.frame_dir, a.model, cfg.seed, dev, record=True)
+        data = frame_dataset_from_dir(a.frame_dir, a.model, cfg.seed, dev, record=True, pad_batches=cfg.pad_variable_length)
         flat = data.model.selector.flatten_parameters(dev).detach().clone()
         if flat.numel() != ops.flat_offsets(cfg.dim)["__total__"][0]:
             ap.error(f"--dim {cfg.dim} does not match the selector of the model")
