@@ -500,6 +500,33 @@ int tspo_preprocess_select(const uint8_t* pool, int layout, int P, int H, int W,
 int tspo_clip_scores(const float* txt, const float* feat, int B, int T, int D, int M, float* clip,
                      tspo_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Several questions about ONE video (the `_questions` entries)
+ * ------------------------------------------------------------------------
+ * The reference's index generation is driven once per question (mp_tools/vlmeval/vlm/gen_id_tspo.py:59-92: the cache is keyed by
+ * the question's index, not by the video), and the benchmarks ask several questions per video.  Only the last step of
+ * MultiModal_Align.forward reads the text (model/temporal_agent.py:135-141; the clip scores of :167 likewise), so for Q
+ * questions about one video the frame features and the text-independent trunk (position add, q|k|v, banded attention, MLP) are
+ * computed once and Q score rows leave.  A caller discovers the capability by symbol lookup (the ABI version is unchanged).
+ *
+ * Contract: every output row is BIT FOR BIT what the per-question entry writes -
+ *   clip[q, :]    of tspo_clip_scores_questions       == tspo_clip_scores(txt[q], feat, B = 1, ..);
+ *   scores[q, :]  of tspo_selector_forward_questions  == tspo_selector_forward_ex(B = 1, img, txt[q], clip[q], .., flags);
+ *   temporal_attn                                     == that call's (it does not depend on the question).
+ * img f32 [T,D] is ONE video; txt f32 [Q,M,D]; clip f32 [Q,T] (NULL = zeros); scores f32 [Q,T]; temporal_attn f32 [T,D]
+ * (nullable).  Q >= 1.  There is no `lengths` argument: one call scores one video, nothing is padded.  The workspace is exactly
+ * tspo_selector_workspace_bytes(1, T, D, H, M, window) - it does not grow with Q - and is NOT valid for a backward call
+ * afterwards (no backward of this form exists: training scores one prompt per video).  flags: those of
+ * tspo_selector_forward_ex, i.e. entry 0 of tspo_selector_supported_flags (which keeps its three entries), same rules.
+ * The usual conventions hold: everything is validated before any device work, nothing is allocated or synchronised, launches go
+ * only on `stream`, and the call can be captured in a graph.                                                               */
+int tspo_clip_scores_questions(const float* txt, const float* feat, int Q, int T, int D, int M, float* clip,
+                               tspo_stream_t stream);
+int tspo_selector_forward_questions(const tspo_selector_weights* w, const float* img, const float* txt, const float* clip,
+                                    int Q, int T, int D, int H, int M, int window, float tau,
+                                    float* scores, float* temporal_attn,
+                                    void* workspace, size_t workspace_bytes, tspo_stream_t stream, int flags);
+
 /* Generic bf16 MFMA GEMM exposed for tests / micro-benchmarks:
  * C[M,N] = A[M,K] * W[N,K]^T (+bias[N]) ; bf16 in, f32 accumulate, out bf16 or f32.
  * K % 64 == 0.  act (bits 0-7): 0 none, 1 quick_gelu.  residual (bf16 [M,N], nullable) is added; it may alias C (the encoder's

@@ -94,6 +94,9 @@ SIGNATURES = {
     "tspo_preprocess_select": (_i, [_p, _i, _i, _i, _i, _p, _i, _p, _p, _i, _i, _p, _p, _i, _i, _i, _i, _p, _i,
                                     C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), _p, _p, _sz, _p, _p, _p, _p, _i, _i]),
     "tspo_clip_scores": (_i, [_p, _p, _i, _i, _i, _i, _p, _p]),
+    "tspo_clip_scores_questions": (_i, [_p, _p, _i, _i, _i, _i, _p, _p]),
+    "tspo_selector_forward_questions": (_i, [C.POINTER(SelectorWeights), _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _p, _p, _p, _sz, _p,
+                                             _i]),
     "tspo_gemm_bf16": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
 }
 

@@ -10,8 +10,8 @@
 #include <type_traits>
 
 #include "common.h"
+#include "score_rows.h"
 
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(2))) float f32x2;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 
@@ -918,28 +918,7 @@ bool band_mfma(int which, const float* qkv, float* ctx, float* P, const float* d
 // s_t = (mean_m h_t.e_m / (|h_t||e_m| + 1e-6) + clip_t) / tau   (temporal_agent.py:106-114,135-141)
 // one wave per (b,t) row; 16-byte loads, |h|^2 together with the first text row's dot products in ONE pass over the row (round 5:
 // three dependent passes of 4-byte loads before - the launch is a latency chain, 9.0 -> 5 us at B T = 1024)
-__device__ __forceinline__ float dot4(const f32x4 a, const f32x4 b) { return (a[0] * b[0] + a[1] * b[1]) + (a[2] * b[2] + a[3] * b[3]); }
-// this lane's share of h.h, h.e and e.e over a row of nv float4 (lane + 64 i): the loads of up to 4 chunks of BOTH rows are issued
-// together, then the arithmetic (D <= 1024: one round trip per row)
-__device__ __forceinline__ void row_dots(const f32x4* __restrict__ hr, const f32x4* __restrict__ er, int nv, int lane, bool want_hh,
-                                         float& hh, float& de, float& ee) {
-  const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-  for (int c0 = lane; c0 < nv; c0 += 256) {
-    f32x4 hv[4], ev[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int c = c0 + 64 * i;
-      hv[i] = c < nv ? hr[c] : z;
-      ev[i] = c < nv ? er[c] : z;
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      if (want_hh) hh += dot4(hv[i], hv[i]);
-      de += dot4(hv[i], ev[i]);
-      ee += dot4(ev[i], ev[i]);
-    }
-  }
-}
+// (dot4 and row_dots: score_rows.h, shared with questions.hip)
 __global__ __launch_bounds__(256) void score_fwd_kernel(const float* __restrict__ h, const float* __restrict__ txt,
                                                         const float* __restrict__ clip, float* __restrict__ scores,
                                                         int B, int T, int D, int M, float tau,
@@ -1852,20 +1831,23 @@ extern "C" size_t tspo_selector_workspace_bytes(int B, int T, int D, int H, int 
   return carve(nullptr, B, T, D, H, M, window).bytes;
 }
 
+// questions = Q > 0 (tspo_selector_forward_questions): img is ONE video (B = 1), txt [Q, M, D], clip / scores [Q, T]; the trunk runs
+// once and the scoring tail is questions.hip's (scores[q, :] bit for bit those of a call with txt[q], clip[q]).
 static int selector_forward_impl(const tspo_selector_weights* w, const float* img, const float* txt,
                                  const float* clip, int B, int T, int D, int H, int M, int window, float tau,
                                  float* scores, float* temporal_attn, void* workspace, size_t workspace_bytes,
-                                 tspo_stream_t stream, int flags, const int32_t* lengths = nullptr, int min_length = 0) {
+                                 tspo_stream_t stream, int flags, const int32_t* lengths = nullptr, int min_length = 0,
+                                 int questions = 0, const char* fn = "selector_forward") {
   Prec prec;
-  if (int e = sel_prec("selector_forward", 0, flags, D, &prec)) return e;
-  TSPO_REQUIRE(!lengths || (min_length >= 1 && min_length <= T), "selector_forward: min_length=%d must be in [1, T=%d]", min_length, T);
-  TSPO_REQUIRE(w && img && txt && scores && workspace, "selector_forward: null pointer");
-  TSPO_REQUIRE(w->wqkv && w->bqkv && w->w1 && w->b1 && w->w2 && w->b2, "selector_forward: null weight pointer");
-  if (int e = check_dims("selector_forward", B, T, D, H, M, window)) return e;
-  TSPO_REQUIRE(tau != 0.f, "selector_forward: score_tau must be non-zero");
+  if (int e = sel_prec(fn, 0, flags, D, &prec)) return e;
+  TSPO_REQUIRE(!lengths || (min_length >= 1 && min_length <= T), "%s: min_length=%d must be in [1, T=%d]", fn, min_length, T);
+  TSPO_REQUIRE(w && img && txt && scores && workspace, "%s: null pointer", fn);
+  TSPO_REQUIRE(w->wqkv && w->bqkv && w->w1 && w->b1 && w->w2 && w->b2, "%s: null weight pointer", fn);
+  if (int e = check_dims(fn, B, T, D, H, M, window)) return e;
+  TSPO_REQUIRE(tau != 0.f, "%s: score_tau must be non-zero", fn);
   SelWs s = carve(workspace, B, T, D, H, M, window);
   if (workspace_bytes < s.bytes)
-    return tspo::set_err(TSPO_EWORKSPACE, "selector_forward: workspace %zu < %zu", workspace_bytes, s.bytes);
+    return tspo::set_err(TSPO_EWORKSPACE, "%s: workspace %zu < %zu", fn, workspace_bytes, s.bytes);
   hipStream_t st = (hipStream_t)stream;
   const int BT = B * T;
   const size_t tot = (size_t)BT * D;
@@ -1879,13 +1861,16 @@ static int selector_forward_impl(const tspo_selector_weights* w, const float* im
                        D, H, window, lengths, min_length);
   if (int e = launch_gemm_nt<EPI_RELU>(s.ctx, w->w1, w->b1, nullptr, s.h1, BT, D, D, st, prec)) return e;
   if (int e = launch_gemm_nt<EPI_RESID>(s.h1, w->w2, w->b2, img, s.h2, BT, D, D, st, prec)) return e;
-  hipLaunchKernelGGL(score_fwd_kernel, dim3((BT + 3) / 4), dim3(256), 0, st, s.h2, txt, clip, scores, B, T, D, M, tau,
-                     lengths, min_length);
+  if (questions)
+    tspo::launch_score_questions(s.h2, txt, clip, scores, questions, T, D, M, tau, st);
+  else
+    hipLaunchKernelGGL(score_fwd_kernel, dim3((BT + 3) / 4), dim3(256), 0, st, s.h2, txt, clip, scores, B, T, D, M, tau,
+                       lengths, min_length);
   if (temporal_attn) {
     hipError_t e = hipMemcpyAsync(temporal_attn, s.h2, tot * sizeof(float), hipMemcpyDeviceToDevice, st);
-    if (e != hipSuccess) return tspo::set_err(TSPO_ELAUNCH, "selector_forward: copy: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return tspo::set_err(TSPO_ELAUNCH, "%s: copy: %s", fn, hipGetErrorString(e));
   }
-  return tspo::check_launch("selector_forward");
+  return tspo::check_launch(fn);
 }
 
 extern "C" int tspo_selector_forward(const tspo_selector_weights* w, const float* img, const float* txt,
@@ -1908,6 +1893,14 @@ extern "C" int tspo_selector_forward_len(const tspo_selector_weights* w, const f
                                          tspo_stream_t stream, int flags, const int32_t* lengths, int min_length) {
   return selector_forward_impl(w, img, txt, clip, B, T, D, H, M, window, tau, scores, temporal_attn, workspace,
                                workspace_bytes, stream, flags, lengths, min_length);
+}
+extern "C" int tspo_selector_forward_questions(const tspo_selector_weights* w, const float* img, const float* txt,
+                                               const float* clip, int Q, int T, int D, int H, int M, int window, float tau,
+                                               float* scores, float* temporal_attn, void* workspace,
+                                               size_t workspace_bytes, tspo_stream_t stream, int flags) {
+  TSPO_REQUIRE(Q >= 1 && Q <= 1000000, "selector_forward_questions: bad dims Q=%d (1..1000000)", Q);
+  return selector_forward_impl(w, img, txt, clip, 1, T, D, H, M, window, tau, scores, temporal_attn, workspace,
+                               workspace_bytes, stream, flags, nullptr, 0, Q, "selector_forward_questions");
 }
 
 namespace {

@@ -13,7 +13,7 @@ from __future__ import annotations
 import json
 import os
 import pickle
-from typing import Callable, Dict, Iterable, List, Optional
+from typing import Callable, Dict, Iterable, Iterator, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -125,6 +125,7 @@ class FrameIdGenerator:
         self.save_root, self.sample_num, self.load_video = save_root, sample_num, load_video
         self.encode_chunk_frames = encode_chunk_frames
         self.cache_hits = self.cache_misses = 0
+        self.videos_encoded = 0     # extract_feature / extract_feature_questions calls: one per generate_inner miss, one per generate_video with a miss
 
     @staticmethod
     def problem_of(question: str) -> str:
@@ -153,10 +154,70 @@ class FrameIdGenerator:
             save_feature_cache(path, image, text, clip, sampled_idx)
             sampled_idx = torch.as_tensor(sampled_idx)
             self.cache_misses += 1
+            self.videos_encoded += 1
         else:
             image, text, clip, sampled_idx = load_feature_cache(path, model.device, model.dtype)
             self.cache_hits += 1
         return select_frame_ids(model, image, text, clip, sampled_idx, dataset, self.sample_num)
+
+
+    def generate_video(self, video_path: str, items: Sequence[Tuple[object, str]], dataset: str) -> Dict[object, List[float]]:
+        """Every question the benchmark asks about ONE video in one pass: items = [(index, question), ...] ->
+        {index: [float absolute frame numbers]}, each list what `generate_inner` returns for that index.  Indices whose .pth
+        exists are served from it; if any is missing, the video is decoded once and encoded once
+        (`extract_feature_questions`), every missing index gets the per-index cache file `generate_inner` would have written
+        (the harness and later `generate_inner` calls hit it), and their selections are one batched call
+        (`temporal_sampling_questions`).  `cache_hits` / `cache_misses` count per index, `videos_encoded` per encode."""
+        assert dataset in DATASET_METHOD
+        model = self.tspo_model
+        out: Dict[object, List[float]] = {}
+        missing = []
+        for index, question in items:
+            path = feature_cache_path(self.save_root, dataset, index)
+            if os.path.exists(path):
+                image, text, clip, sampled_idx = load_feature_cache(path, model.device, model.dtype)
+                self.cache_hits += 1
+                out[index] = select_frame_ids(model, image, text, clip, sampled_idx, dataset, self.sample_num)
+            else:
+                missing.append((index, self.problem_of(question), path))
+        if missing:
+            if self.load_video is None:
+                raise FileNotFoundError(f"{missing[0][2]} is not cached and no load_video plug-in was given")
+            video, _, _, sampled_idx = self.load_video(video_path, max_frames_num=50000, fps=1, force_sample=False)
+            problems = [p for _, p, _ in missing]
+            before = getattr(model, "encode_chunk_frames", None)
+            if self.encode_chunk_frames is not None:
+                model.encode_chunk_frames = self.encode_chunk_frames
+            try:
+                image, texts, clips = model.extract_feature_questions(self.clip_processor, video, problems)
+            finally:
+                if self.encode_chunk_frames is not None:
+                    model.encode_chunk_frames = before
+            self.videos_encoded += 1
+            for q, (_, _, path) in enumerate(missing):
+                save_feature_cache(path, image, texts[q], clips[q], sampled_idx)
+                self.cache_misses += 1
+            abs_idx = torch.as_tensor(sampled_idx)
+            if len(image) > self.sample_num:      # select_frame_ids' rule, for all missing questions at once
+                with torch.no_grad():
+                    ts_ids, _ = model.temporal_sampling_questions(image, texts, clips, DATASET_METHOD[dataset], 12, self.sample_num)
+                ts_ids = ts_ids.cpu()
+                for q, (index, _, _) in enumerate(missing):
+                    out[index] = abs_idx[ts_ids[q]].float().tolist()
+            else:
+                for index, _, _ in missing:
+                    out[index] = abs_idx.float().tolist()
+        return {index: out[index] for index, _ in items}
+
+
+def group_by_video(messages_with_index: Iterable[Tuple[object, Sequence[dict]]]) -> Iterator[Tuple[str, List[Tuple[object, str]]]]:
+    """(index, message) pairs of the harness (message = [{"value": video_path}, {"value": question}], as `generate_inner` takes
+    it) -> (video_path, [(index, question), ...]) groups for `FrameIdGenerator.generate_video`: videos in first-seen order, the
+    questions of a video in the order they came."""
+    groups: Dict[str, List[Tuple[object, str]]] = {}
+    for index, message in messages_with_index:
+        groups.setdefault(message[0]["value"], []).append((index, message[1]["value"]))
+    yield from groups.items()
 
 
 def extract_selector_state(state: Dict[str, torch.Tensor], prefix: Optional[str] = None) -> Dict[str, torch.Tensor]:

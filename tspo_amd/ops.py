@@ -309,6 +309,34 @@ def selector_forward(flat: torch.Tensor, img: torch.Tensor, txt: torch.Tensor, c
     return scores, attn, ws
 
 
+def selector_forward_questions(flat: torch.Tensor, img: torch.Tensor, txt: torch.Tensor, clip: Optional[torch.Tensor],
+                               heads: int, window: int, tau: float, precision: str = "fp32", want_attn: bool = True,
+                               ws: Optional[torch.Tensor] = None):
+    """Q questions about ONE video: img [T,D], txt [Q,M,D], clip [Q,T] | None -> (scores [Q,T] f32, temporal_attn [T,D] f32 | None).
+    The trunk runs once; scores[q] are bit for bit selector_forward(flat, img[None], txt[q][None], clip[q][None], ..)[0][0] at
+    the same `precision` (the names selector_forward takes).  Inference only: the workspace (that of B = 1, whatever Q; `ws` to
+    reuse one) is not valid for a backward."""
+    _need_gpu(flat, img, txt, clip)
+    assert flat.dtype == torch.float32 and flat.is_contiguous()
+    x, e = _f32c(img), _f32c(txt)
+    if x.dim() != 2 or e.dim() != 3 or e.shape[2] != x.shape[1]:
+        raise ValueError(f"selector_forward_questions: img must be [T,D] and txt [Q,M,D], got {tuple(x.shape)} and {tuple(e.shape)}")
+    T, D = x.shape
+    Q, M = e.shape[0], e.shape[1]
+    c = _f32c(clip) if clip is not None else None
+    if c is not None and tuple(c.shape) != (Q, T):
+        raise ValueError(f"selector_forward_questions: clip must be [Q,T] = {(Q, T)}, got {tuple(c.shape)}")
+    if ws is None:
+        ws = selector_workspace(1, T, D, heads, M, window, x.device)
+    scores = torch.empty((Q, T), dtype=torch.float32, device=x.device)
+    attn = torch.empty((T, D), dtype=torch.float32, device=x.device) if want_attn else None
+    w = _sel_structs(flat, D, _lib.SelectorWeights)
+    check(_lib.lib().tspo_selector_forward_questions(C.byref(w), _ptr(x), _ptr(e), _ptr(c), Q, T, D, int(heads), M, int(window),
+                                                     float(tau), _ptr(scores), _ptr(attn), _ptr(ws), ws.numel(), _stream(),
+                                                     _sel_flags(precision, forward=True)), "tspo_selector_forward_questions")
+    return scores, attn
+
+
 def selector_backward(flat: torch.Tensor, flat_grad: torch.Tensor, img, txt, dscores, H, window, tau, ws,
                       precision: str = "fp32", accumulate: bool = False, lengths=None, min_length: Optional[int] = None):
     """Writes the gradient of every trainable tensor into `flat_grad` (same layout as `flat`); accumulate=True ADDS it to what
@@ -639,6 +667,20 @@ def clip_scores(txt: torch.Tensor, feat: torch.Tensor) -> torch.Tensor:
     B, T, D = f.shape
     out = torch.empty((B, T), dtype=torch.float32, device=f.device)
     check(_lib.lib().tspo_clip_scores(_ptr(e), _ptr(f), B, T, D, e.shape[1], _ptr(out), _stream()), "tspo_clip_scores")
+    return out
+
+
+def clip_scores_questions(txt: torch.Tensor, feat: torch.Tensor) -> torch.Tensor:
+    """txt [Q,M,D] (row 0 of each question used), feat [T,D] of ONE video -> cosine [Q,T]; row q is bit for bit
+    clip_scores(txt[q][None], feat[None])[0], from one pass over the frames."""
+    _need_gpu(txt, feat)
+    e, f = _f32c(txt), _f32c(feat)
+    if f.dim() != 2 or e.dim() != 3 or e.shape[2] != f.shape[1]:
+        raise ValueError(f"clip_scores_questions: feat must be [T,D] and txt [Q,M,D], got {tuple(f.shape)} and {tuple(e.shape)}")
+    T, D = f.shape
+    out = torch.empty((e.shape[0], T), dtype=torch.float32, device=f.device)
+    check(_lib.lib().tspo_clip_scores_questions(_ptr(e), _ptr(f), e.shape[0], T, D, e.shape[1], _ptr(out), _stream()),
+          "tspo_clip_scores_questions")
     return out
 
 

@@ -73,6 +73,27 @@ class FrameScorer:
         idx = ops.topk_sorted(scores, k) if method == "topk" else ops.binmax(scores, k)
         return idx, scores, feats
 
+    def score_questions(self, feats: torch.Tensor, text_features: torch.Tensor, clip_scores: Optional[torch.Tensor] = None):
+        """Q questions about ONE video: feats [T,D], text [Q,M,D] -> (scores f32 [Q,T], clip_scores [Q,T]).  The selector trunk
+        runs once (ops.selector_forward_questions); row q is bit for bit `score(feats[None], text[q][None])`."""
+        if clip_scores is None:
+            clip_scores = ops.clip_scores_questions(text_features, feats)
+        T, D = feats.shape
+        need = ops._lib.lib().tspo_selector_workspace_bytes(1, T, D, self.heads, text_features.shape[1], self.window)
+        if self._sel_ws is None or self._sel_ws.numel() < need:
+            self._sel_ws = torch.empty((need,), dtype=torch.uint8, device=feats.device)
+        scores, _ = ops.selector_forward_questions(self.flat, feats, text_features, clip_scores, self.heads, self.window, self.tau,
+                                                   precision=self.selector_precision, want_attn=False, ws=self._sel_ws)
+        return scores, clip_scores
+
+    def questions(self, pixels: torch.Tensor, text_features: torch.Tensor, k: int, method: str = "topk"):
+        """`__call__` for Q questions about one video: pixels [T,3,H,W] encoded ONCE, text [Q,M,D] ->
+        (idx [Q,k], scores [Q,T], feats [T,D])."""
+        feats = self.encode(pixels)
+        scores, clip = self.score_questions(feats, text_features)
+        idx = ops.topk_sorted(scores, k) if method == "topk" else ops.binmax(scores, k)
+        return idx, scores, feats
+
 
 class RolloutContext:
     """What `PolicyTrainer.rollout` saved for the matching backward: the selector workspace holding the activations

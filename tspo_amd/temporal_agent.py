@@ -255,6 +255,28 @@ class MultiModal_Align(nn.Module):
                                                float(score_tau), precision=self.inference_gemm_precision, **kw)
         return scores, attn
 
+    def forward_questions(self, input_emb, text_emb, clip_scores, window_size, score_tau=0.025):
+        """Q questions about ONE video: input_emb [T,d], text_emb [Q,M,d], clip_scores [Q,T] -> (sim_total [Q,T],
+        temporal_attn [1,T,d]) in input_emb's dtype.  The text-independent trunk runs once (ops.selector_forward_questions); row q
+        is bit for bit `forward(input_emb, text_emb[q], clip_scores[q], window_size, score_tau)[0]`, temporal_attn is that call's.
+        Inference only (honours `inference_gemm_precision`): training scores one prompt per video and keeps `forward_batched`."""
+        T, D = input_emb.shape
+        if window_size is None:
+            raise TypeError("unsupported operand type(s) for //: 'NoneType' and 'int'")
+        if clip_scores is None:
+            raise TypeError("unsupported operand type(s) for +: 'Tensor' and 'NoneType'")
+        if D != self.dim:
+            raise RuntimeError(f"mat1 and mat2 shapes cannot be multiplied ({T}x{D} and {self.dim}x{self.dim})")
+        if text_emb.ndim != 3:
+            raise ValueError(f"forward_questions: text_emb must be [Q,M,d], got {tuple(text_emb.shape)}")
+        if torch.is_grad_enabled() and any(p.requires_grad for _, p in self._trainable_named()):
+            raise RuntimeError("MultiModal_Align.forward_questions is inference only (no backward of the shared-trunk form): call "
+                               "it under torch.no_grad(), or train through forward / forward_batched")
+        scores, attn = ops.selector_forward_questions(self._flat_params(), input_emb, text_emb,
+                                                      clip_scores.reshape(text_emb.shape[0], T), self.num_heads, int(window_size),
+                                                      float(score_tau), precision=self.inference_gemm_precision)
+        return scores.to(input_emb.dtype), attn.unsqueeze(0).to(input_emb.dtype)
+
 
 def _packed_clip(clip_model) -> "ops.ClipVitWeights":
     """The HF module's vision tower packed for the HIP encoder.  The packed bf16 copy is cached on the module, keyed on
@@ -396,21 +418,51 @@ def extract_clip_features_impl(clip_model, clip_processor, candidates, problem, 
     inputs_text = clip_processor(text=problem, return_tensors="pt", padding=True, truncation=True).to(dev)
     with torch.no_grad():
         text_features = _pooled(clip_model.get_text_features(**inputs_text))
+        image_features = _encode_candidates(clip_model, clip_processor, candidates, processor_type, dev, encode_chunk_frames)
+        clip_scores = ops.clip_scores(text_features[:1].float().unsqueeze(0), image_features.unsqueeze(0))[0]
+    dt = clip_model.dtype
+    return image_features.to(dt), text_features, clip_scores.to(dt)
+
+
+def _encode_candidates(clip_model, clip_processor, candidates, processor_type, dev, encode_chunk_frames):
+    """Raw frames -> f32 features [T, proj]: the frame half of extract_clip_features_impl (and of its several-questions form)."""
     if encode_chunk_frames is not None:
         with torch.no_grad():
-            image_features = _image_features_chunked_from_frames(clip_model, clip_processor, candidates, processor_type, dev,
-                                                                 int(encode_chunk_frames))
-            clip_scores = ops.clip_scores(text_features[:1].float().unsqueeze(0), image_features.unsqueeze(0))[0]
-        dt = clip_model.dtype
-        return image_features.to(dt), text_features, clip_scores.to(dt)
+            return _image_features_chunked_from_frames(clip_model, clip_processor, candidates, processor_type, dev,
+                                                       int(encode_chunk_frames))
     pixels = _frames_to_device_u8(candidates, processor_type, dev, clip_processor)
     if pixels is None:   # non-default processor config / ragged frames: the reference's own CPU PIL path
         _warn_pil_fallback()
         image_list = _frames_to_pil(candidates, processor_type)
         pixels = clip_processor(images=image_list, return_tensors="pt", padding=True).to(dev)["pixel_values"]
     with torch.no_grad():
-        image_features = _image_features(clip_model, pixels)
-        clip_scores = ops.clip_scores(text_features[:1].float().unsqueeze(0), image_features.unsqueeze(0))[0]
+        return _image_features(clip_model, pixels)
+
+
+def extract_clip_features_questions_impl(clip_model, clip_processor, candidates, problems, processor_type='llava',
+                                         encode_chunk_frames=None):
+    """extract_clip_features_impl for SEVERAL questions about one video (the harness asks one question per call,
+    gen_id_tspo.py:59-92, and would encode the video again for each): every question's text feature comes from its own
+    get_text_features call, exactly as on the single path (batching the text tower could change low bits); the frames are
+    preprocessed and encoded ONCE; the clip scores of all questions are one pass over the features (ops.clip_scores_questions).
+    -> (image_features [T,D], text_features [Q,M,D], clip_scores [Q,T]); slice q is what extract_clip_features_impl returns for
+    problems[q], bit for bit."""
+    problems = list(problems)
+    if not problems:
+        raise ValueError("extract_feature_questions: no questions")
+    dev = next(clip_model.parameters()).device
+    texts = []
+    for problem in problems:
+        inputs_text = clip_processor(text=problem, return_tensors="pt", padding=True, truncation=True).to(dev)
+        with torch.no_grad():
+            texts.append(_pooled(clip_model.get_text_features(**inputs_text)))
+    if any(t.shape != texts[0].shape for t in texts):
+        raise ValueError("extract_feature_questions: every question must yield the same number of text rows, got "
+                         + str([int(t.shape[0]) for t in texts]))
+    text_features = torch.stack(texts)
+    with torch.no_grad():
+        image_features = _encode_candidates(clip_model, clip_processor, candidates, processor_type, dev, encode_chunk_frames)
+        clip_scores = ops.clip_scores_questions(text_features[:, :1].float(), image_features)
     dt = clip_model.dtype
     return image_features.to(dt), text_features, clip_scores.to(dt)
 
@@ -448,6 +500,23 @@ class TSPOModel(CLIPModel):
         pred_score, _ = self.selector(image_features, text_features, clip_scores, window_size=window_size)
         ts_ids, _ = self.inference_ts(pred_score, method=method, sample_len=sample_num)
         return ts_ids, pred_score
+
+    def extract_feature_questions(self, clip_processor, candidates, problems, processor_type='llava'):
+        """Several questions about one video: frames encoded once -> (image_features [T,D], text_features [Q,M,D],
+        clip_scores [Q,T]); slice q is `extract_feature(clip_processor, candidates, problems[q])`, bit for bit."""
+        return extract_clip_features_questions_impl(self, clip_processor, candidates, problems, processor_type,
+                                                    encode_chunk_frames=self.encode_chunk_frames)
+
+    def temporal_sampling_questions(self, image_features, text_features, clip_scores, method, window_size, sample_num):
+        """image_features [T,D], text_features [Q,M,D], clip_scores [Q,T] -> (ts_ids [Q,k], pred_scores [Q,T]); row q is
+        `temporal_sampling(image_features, text_features[q], clip_scores[q], ..)`.  'topk' / 'bin-max': one batched sampler call;
+        'aks' runs on the host row by row, as on the single path."""
+        pred_scores, _ = self.selector.forward_questions(image_features, text_features, clip_scores, window_size=window_size)
+        if method == "aks":
+            ts_ids = torch.stack([self.inference_ts(row, method=method, sample_len=sample_num)[0] for row in pred_scores])
+        else:
+            ts_ids, _ = self.inference_ts(pred_scores, method=method, sample_len=sample_num)
+        return ts_ids, pred_scores
 
     def forward(self, clip_processor, candidates, problem, sample_num, window_size=12, method='topk',
                 processor_type='llava'):
